@@ -15,6 +15,11 @@ Prints ONE JSON line on rank 0 (DESIGN.md section 6 explains every field):
                 straggler tail of one launch overlaps the bulk of the next (max-over-ranks time, barrier + synchronize on
                 both sides; kernel trace of the overlap: profiles/r04_pipelined_overlap.json).  This is the throughput a
                 stream of batches gets (varpro_amd.FitPipeline is the product-side form of the same schedule)
+  ms_per_step   the wall time of one of those K steps
+
+A plain run does only that: set up, W warm-up steps, the K timed steps, the line.  --dump-outputs DIR also writes what
+the last timed step computed (dump_outputs).  Everything below is measured with --full only, which also writes the full
+record with its prose to bench_full.json:
   config.one_batch_at_a_time   the same K steps strictly one after another on one stream (rounds 1-3 quoted this as `value`;
                 the number that per-kernel durations reproduce: roofline_fit.single_launch_* come from this loop)
   roofline      the stand-alone Phi/dPhi kernel (vp_basis) against the HBM roofline, HIP-event timed live
@@ -240,6 +245,29 @@ def emit(out):
     return line
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dn, alpha, report, summary):
+    """What the last timed step handed its caller, as DIR/<name>.npy in float64: the fitted parameters alpha (B, q), the
+    report's termination / n_evals / objective (B,) and the step's 4-double summary {sum cost, #ok, #failed, sum evaluations}
+    (all-reduced over the ranks).  Above DUMP_LIMIT_BYTES the per-problem arrays keep a fixed, seeded sample of rows, whose
+    indices are written as problem_index.npy.  The per-problem arrays repeat bit for bit from run to run; the summary's sum
+    of costs does to rounding only (summary_kernel adds its workgroups' partial sums atomically, in no fixed order)."""
+    per_problem = {"alpha": alpha.astype(np.float64)}
+    for k in ("termination", "n_evals", "objective"):
+        per_problem[k] = report[k].astype(np.float64)
+    n = alpha.shape[0]
+    row_bytes = sum(a[:1].nbytes for a in per_problem.values()) + 8
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, (DUMP_LIMIT_BYTES - 1024) // row_bytes, replace=False))
+        per_problem = {k: a[rows] for k, a in per_problem.items()}
+        per_problem["problem_index"] = rows.astype(np.float64)
+    os.makedirs(dn, exist_ok=True)
+    for k, a in dict(per_problem, summary=np.asarray(summary, dtype=np.float64)).items():
+        np.save(os.path.join(dn, k + ".npy"), np.ascontiguousarray(a))
+
+
 # taken NOW: importing torch initialises its OpenMP runtime, which under OMP_PROC_BIND pins the main thread to one
 # place -- the affinity mask read afterwards would show a single core
 CPU_TOPOLOGY = cpu_topology()
@@ -262,6 +290,11 @@ def main():
                     help="N = 1 only: run the G per-GPU shards of BASELINE configs[3] (G x batch problems) one after another "
                          "on this device and report per-shard time / evaluations and the predicted weak-scaling efficiency "
                          "mean/max (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the one-batch-at-a-time loop, the rooflines, the "
+                         "configs[0,1,2,4] side measurements, the CPU baseline and the parity census, and bench_full.json")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (the arrays its caller receives) as DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -336,6 +369,7 @@ def main():
     bp = handles[0]
 
     fit_events = []  # (start, end) HIP events around the fit of every TIMED step (recorded on the launch stream, no host sync)
+    last_fit = [None]  # (alpha, C, report) the latest step's fit returned to its caller (--dump-outputs)
 
     def step(k, nslots, events=None):
         # everything is enqueued asynchronously: the fit kernel, the 4-double batch summary (device side) and
@@ -345,7 +379,7 @@ def main():
             if events is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            handles[i].fit(guesses[i], want_coefficients=False)
+            last_fit[0] = handles[i].fit(guesses[i], want_coefficients=False)
             if events is not None:
                 e1.record()
                 events.append((e0, e1))
@@ -384,9 +418,13 @@ def main():
             dt_ = float(tmax.item())
         return dt_, last_
 
-    dt_one, last = timed(1)        # K steps strictly one batch at a time (single-launch durations: fit_events)
-    dt, _last2 = timed(2)          # THE timed region: the same K steps, two batches in flight (handle / stream k mod 2)
-    last = last.cpu().numpy()
+    if args.full:
+        dt_one, _ = timed(1)       # K steps strictly one batch at a time (single-launch durations: fit_events)
+    dt, last_red = timed(2)        # THE timed region: the same K steps, two batches in flight (handle / stream k mod 2)
+    if args.dump_outputs and rank == 0:
+        alpha_l, _c, rep_l = last_fit[0]
+        dump_outputs(args.dump_outputs, alpha_l.cpu().numpy(), bp.report_to_numpy(rep_l), last_red.cpu().numpy())
+    last = reds[0].cpu().numpy()   # the totals of handle 0's batch (problems first .. first + B - 1), all-reduced over the ranks
     total_fits = float(world) * B * args.steps
     value = total_fits / dt
     sum_cost, n_ok, n_bad, n_evals = [float(v) for v in last]
@@ -395,6 +433,36 @@ def main():
     out = None
     cfg4_check = None
     if rank == 0:
+        out = {
+            "metric": "independent fits/sec (double-exp, m=%d, fp64)" % m,
+            "value": value,
+            "unit": "fits/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "schema": 3,  # 1 (rounds 1-3): value = one batch at a time; 2 (round 4): two batches in flight on the SAME data;
+                          # 3: two batches in flight on two different batches.  config.one_batch_at_a_time keeps definition 1
+            "value_definition": "K complete batched fits, two batches in flight (handle / HIP stream k mod 2, two different batches)",
+            "config": {
+                "workload": "B=%d fits/GPU, m=%d, fp64, double-exp+offset (n=3, q=2), one full LM fit per step" % (B, m),
+                "workload_detail": "BASELINE configs[3] per-GPU shard = north_star 1-GPU headline; noise %.0e; two batches in "
+                                   "flight (step k on handle / HIP stream k mod 2); every step starts from the initial guesses" % args.noise,
+                "batch_per_gpu": B, "m": m, "parallelism": "batch-sharded x%d" % world,
+                "batches_in_flight": 2,
+                "world_size": dist.get_world_size() if use_dist else 1,
+                "collective_backend": ("rccl (torch.distributed nccl)" if backend == "nccl" else backend) if use_dist else None,
+                "per_rank_ms_per_step": [t_ / args.steps * 1e3 for t_ in per_rank_s.get(2, [dt])],
+                "mean_evaluations_per_fit": evals_per_fit, "fits_successful": n_ok, "fits_failed": n_bad,
+                "sum_cost": sum_cost,
+            },
+        }
+    if rank == 0 and args.full:
         T = 8
 
         def event_ms(fn, reps, warm=2):
@@ -535,67 +603,38 @@ def main():
         flops_eval = m * 2 * 28 + 2 * m * 9 + 4 * m * 3 + (4 * 3 + 2) * m * 2
         tflops_fit = B * evals_per_fit * flops_eval / (fit_ms * 1e-3) / 1e12
         tflops_dev = B * evals_per_fit * flops_eval * args.steps / dt / 1e12   # device-level: the whole timed region
-        out = {
-            "metric": "independent fits/sec (double-exp, m=%d, fp64)" % m,
-            "value": value,
-            "unit": "fits/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "schema": 3,  # 1 (rounds 1-3): value = one batch at a time; 2 (round 4): two batches in flight on the SAME data;
-                          # 3: two batches in flight on two different batches.  config.one_batch_at_a_time keeps definition 1
-            "value_definition": "K complete batched fits, two batches in flight (handle / HIP stream k mod 2, two different batches)",
-            "config": {
-                "workload": "B=%d fits/GPU, m=%d, fp64, double-exp+offset (n=3, q=2), one full LM fit per step" % (B, m),
-                "workload_detail": "BASELINE configs[3] per-GPU shard = north_star 1-GPU headline; noise %.0e; two batches in "
-                                   "flight (step k on handle / HIP stream k mod 2); every step starts from the initial guesses" % args.noise,
-                "batch_per_gpu": B, "m": m, "parallelism": "batch-sharded x%d" % world,
-                "batches_in_flight": 2,
-                "world_size": dist.get_world_size() if use_dist else 1,
-                "collective_backend": ("rccl (torch.distributed nccl)" if backend == "nccl" else backend) if use_dist else None,
-                "one_batch_at_a_time": {
-                    "fits_per_s": total_fits / dt_one, "ms_per_step": dt_one / args.steps * 1e3,
-                    "per_rank_ms_per_step": [t_ / args.steps * 1e3 for t_ in per_rank_s.get(1, [dt_one])],
-                    "note": "the same K steps strictly one after another on one HIP stream (what rounds 1-3 quoted as `value`): a "
-                            "launch ends with its longest fits (> 100 LM evaluations against a mean of 9) running alone, ~0.5 ms "
-                            "in which most of the device idles; with two batches in flight that tail overlaps the bulk of the "
-                            "next batch (kernel trace: profiles/r04_pipelined_overlap.json)"},
-                "per_rank_ms_per_step": [t_ / args.steps * 1e3 for t_ in per_rank_s.get(2, [dt])],
-                "mean_evaluations_per_fit": evals_per_fit, "fits_successful": n_ok, "fits_failed": n_bad,
-                "sum_cost": sum_cost,
-            },
-            "roofline": {
-                "kernel": "basis_flat_kernel (vp_basis: stand-alone Phi/dPhi evaluation; one thread per row pair of one column: "
-                          "Phi and dPhi are each written as one linear sweep)",
-                "dominant_kernel": False, "dominant_kernel_roofline": "roofline_fit (fit2_kernel: the timed step is one launch of it; "
-                "bound by the fp64 vector ALU, which the roofline contract's hbm / mfma bounds cannot express)",
-                "bound": "hbm", "achieved": gbs_phi, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": gbs_phi / HBM_PEAK_GBS, "traffic": committed_traffic("basis_flat_kernel") or committed_traffic("basis_rowpair_kernel"),
-                "traffic_source": traffic_source("basis_flat_kernel") or traffic_source("basis_rowpair_kernel"),
-                "bytes_per_launch": bytes_phi, "avg_launch_ms": basis_ms, "back_to_back_ms_per_launch": basis_ms_back_to_back,
-            },
-            "roofline_fit": {
-                "kernel": "fit2_kernel (vp_fit: persistent slot kernel, dominant kernel of the timed step)",
-                "dominant_kernel": True,
-                "bound": "fp64_valu", "achieved": tflops_dev, "peak": FP64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": tflops_dev / FP64_VALU_PEAK_TFLOPS, "flops_per_evaluation": flops_eval,
-                "what": "achieved = algorithmic fp64 flops of the K timed steps / the timed region (two launches share the device, "
-                        "so the device-level rate is the one that can be set against the device's peak); single_launch_* = one "
-                        "launch alone on the device, HIP-event pairs around vp_fit inside the one-batch-at-a-time loop (what a "
-                        "kernel trace of that loop reports per dispatch)",
-                "single_launch_avg_ms": fit_ms, "single_launch_achieved": tflops_fit,
-                "single_launch_frac": tflops_fit / FP64_VALU_PEAK_TFLOPS,
-                "hbm_achieved_GBps": gbs_fit, "hbm_frac": gbs_fit / HBM_PEAK_GBS, "traffic": committed_traffic("fit2_kernel"),
-                "traffic_source": traffic_source("fit2_kernel"),
-                "valu_issue_frac": committed_valu_issue("fit2_kernel")[0], "valu_issue_source": committed_valu_issue("fit2_kernel")[1],
-                "bytes_per_launch": bytes_fit, "avg_launch_ms": fit_ms, "fits_per_s_kernel_only": B / (fit_ms * 1e-3),
-            },
+        out["config"]["one_batch_at_a_time"] = {
+            "fits_per_s": total_fits / dt_one, "ms_per_step": dt_one / args.steps * 1e3,
+            "per_rank_ms_per_step": [t_ / args.steps * 1e3 for t_ in per_rank_s.get(1, [dt_one])],
+            "note": "the same K steps strictly one after another on one HIP stream (what rounds 1-3 quoted as `value`): a "
+                    "launch ends with its longest fits (> 100 LM evaluations against a mean of 9) running alone, ~0.5 ms "
+                    "in which most of the device idles; with two batches in flight that tail overlaps the bulk of the "
+                    "next batch (kernel trace: profiles/r04_pipelined_overlap.json)"}
+        out["roofline"] = {
+            "kernel": "basis_flat_kernel (vp_basis: stand-alone Phi/dPhi evaluation; one thread per row pair of one column: "
+                      "Phi and dPhi are each written as one linear sweep)",
+            "dominant_kernel": False, "dominant_kernel_roofline": "roofline_fit (fit2_kernel: the timed step is one launch of it; "
+            "bound by the fp64 vector ALU, which the roofline contract's hbm / mfma bounds cannot express)",
+            "bound": "hbm", "achieved": gbs_phi, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": gbs_phi / HBM_PEAK_GBS, "traffic": committed_traffic("basis_flat_kernel") or committed_traffic("basis_rowpair_kernel"),
+            "traffic_source": traffic_source("basis_flat_kernel") or traffic_source("basis_rowpair_kernel"),
+            "bytes_per_launch": bytes_phi, "avg_launch_ms": basis_ms, "back_to_back_ms_per_launch": basis_ms_back_to_back,
+        }
+        out["roofline_fit"] = {
+            "kernel": "fit2_kernel (vp_fit: persistent slot kernel, dominant kernel of the timed step)",
+            "dominant_kernel": True,
+            "bound": "fp64_valu", "achieved": tflops_dev, "peak": FP64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": tflops_dev / FP64_VALU_PEAK_TFLOPS, "flops_per_evaluation": flops_eval,
+            "what": "achieved = algorithmic fp64 flops of the K timed steps / the timed region (two launches share the device, "
+                    "so the device-level rate is the one that can be set against the device's peak); single_launch_* = one "
+                    "launch alone on the device, HIP-event pairs around vp_fit inside the one-batch-at-a-time loop (what a "
+                    "kernel trace of that loop reports per dispatch)",
+            "single_launch_avg_ms": fit_ms, "single_launch_achieved": tflops_fit,
+            "single_launch_frac": tflops_fit / FP64_VALU_PEAK_TFLOPS,
+            "hbm_achieved_GBps": gbs_fit, "hbm_frac": gbs_fit / HBM_PEAK_GBS, "traffic": committed_traffic("fit2_kernel"),
+            "traffic_source": traffic_source("fit2_kernel"),
+            "valu_issue_frac": committed_valu_issue("fit2_kernel")[0], "valu_issue_source": committed_valu_issue("fit2_kernel")[1],
+            "bytes_per_launch": bytes_fit, "avg_launch_ms": fit_ms, "fits_per_s_kernel_only": B / (fit_ms * 1e-3),
         }
 
         # ================= side measurements: BASELINE configs[0], [1], [2], [4] (rank 0, N = 1 only) =================
@@ -1154,7 +1193,7 @@ def main():
             bpg.close()
 
     # ---- CPU baseline: the oracle (port of the reference algorithm) on the host cores, rank 0, N=1 only ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         cpu_model, sockets, phys_cores, usable, quota = CPU_TOPOLOGY
         # one pinned thread per physical core, capped by the container's CPU bandwidth quota (a cgroup limit of N CPUs
@@ -1246,7 +1285,7 @@ def main():
             out["build"].update(json.load(open(os.path.join(ROOT, "varpro_amd", "lib", "build_info.json"))))
         except Exception:
             pass
-        line = emit(out)
+        line = emit(out) if args.full else json.dumps(compact(out), separators=(",", ":"))
         print(line, flush=True)
     for h_ in handles:
         h_.close()

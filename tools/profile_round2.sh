@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/$TAG
 rm -rf $OUT; mkdir -p $OUT/summary
-CMD="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --emulate-shards 0"
+CMD="python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --emulate-shards 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o $TAG -- $CMD > $OUT/summary/${TAG}_bench_under_rocprof_stdout.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -o $TAG -- $CMD > $OUT/bench_pmc_fetch_stdout.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -o $TAG -- $CMD > $OUT/bench_pmc_write_stdout.log 2>&1
@@ -43,7 +43,7 @@ for k, s, e, g, q, v, sc in trace: agg[(k, g)].append(e - s)
 rows = [{"kernel": k, "grid_size": g, "calls": len(v), "avg_us": sum(v) / len(v) / 1e3, "min_us": min(v) / 1e3, "max_us": max(v) / 1e3,
          "total_ms": sum(v) / 1e6} for (k, g), v in agg.items()]
 rows.sort(key=lambda r: -r["total_ms"])
-json.dump({"command": "rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline", "kernels": rows},
+json.dump({"command": "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline", "kernels": rows},
           open(out + "/summary/%s_bench_kernel_stats.json" % tag, "w"), indent=1)
 for r in rows[:14]: print("%-34s grid %9d calls %4d avg %9.1f us  total %8.2f ms" % (r["kernel"], r["grid_size"], r["calls"], r["avg_us"], r["total_ms"]))
 # pipelined overlap: the headline-size fit launches, in start order; the pipelined leg alternates two queues
@@ -71,7 +71,7 @@ for kind, ctr in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE")):
     for (name, grid), v in d.items():
         e = res.setdefault("%s@grid%d" % (name, grid), {"kernel": name, "grid_size": grid})
         e[ctr + "_KiB_per_launch"] = sum(v) / len(v); e["launches_" + ctr] = len(v)
-tr = {"command": "python bench.py --steps 10 --warmup 2 --no-cpu-baseline (tools/profile_round2.sh; separate --pmc FETCH_SIZE and --pmc WRITE_SIZE passes, --kernel-trace only)",
+tr = {"command": "python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline (tools/profile_round2.sh; separate --pmc FETCH_SIZE and --pmc WRITE_SIZE passes, --kernel-trace only)",
       "correction": "gfx950: FETCH_SIZE reports 1/2 of wide coalesced streaming reads (MI355X_MICROARCH.md HBM section) -> hbm bytes = WRITE_SIZE + 2*FETCH_SIZE; counters are in KiB",
       "per_kernel_and_grid": {}}
 big = {}
