@@ -82,6 +82,8 @@ extern "C" {
         rep: *mut vp_report, trace_out: *mut f64, trace_rows: i32) -> i32;
     pub fn vp_statistics(h: *mut vp_batch, cov_out: *mut c_void, chi2_out: *mut f64, sigma_out: *mut c_void,
         status: *mut i32) -> i32;
+    pub fn vp_global_statistics(h: *mut vp_batch, cov_alpha_out: *mut c_void, chi2_out: *mut f64, coef_cov_out: *mut c_void,
+        coef_alpha_cov_out: *mut c_void, sigma_out: *mut c_void, status: *mut i32) -> i32;
     pub fn vp_set_rhs_allreduce(h: *mut vp_batch,
         f: Option<extern "C" fn(*mut c_void, i64, *mut c_void, *mut c_void) -> i32>, user: *mut c_void,
         global_rhs_count: i64) -> i32;

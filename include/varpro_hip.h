@@ -119,8 +119,9 @@ enum {
                               * accepted for every entry point -- shapes without a specialised kernel set run on generic
                               * kernels, global fits (S > 1) and any batch size included; m < n (an underdetermined
                               * linear sub-problem) takes the reference's minimum-norm solution; right-hand-side sharding
-                              * (vp_set_rhs_allreduce) works on every shape.  What remains unsupported: fit statistics with
-                              * S > 1 (as in the reference), vp_debug_gram_evaluate on handles without the Gram kernel */
+                              * (vp_set_rhs_allreduce) works on every shape.  What remains unsupported: vp_statistics with
+                              * S > 1 (as in the reference; vp_global_statistics covers global fits), vp_global_statistics
+                              * of sharded right-hand sides, vp_debug_gram_evaluate on handles without the Gram kernel */
     VP_ERR_HIP = -3,         /* HIP runtime failure */
     VP_ERR_NO_DEVICE = -4    /* no gfx950 device / library built without device code */
 };
@@ -415,6 +416,33 @@ int vp_best_fit(vp_batch *h, void *fit_out);
  *   status             [B] or NULL        0 ok; 4 = Underdetermined / MatrixInversion (the reference's Err)
  */
 int vp_statistics(vp_batch *h, void *cov_out, double *reduced_chi2_out, void *conf_sigma_out, int32_t *status);
+
+/*
+ * Fit statistics of a GLOBAL fit (one alpha shared by the S right-hand sides of a problem, any S >= 1): the open item
+ * "Fit statistics (and confidence bands, but also correlation matrix etc) for problems with multiple RHS" of the
+ * reference's Todo.md, answered by FitStatistics::try_calculate (src/statistics/mod.rs:352-441) applied unchanged to the
+ * equivalent single-RHS problem: observations vec(Y) (m S rows, stacked weights), parameters [c_1 .. c_S, alpha]
+ * (n S + q), model (I_S (x) Phi(alpha)) vec(C).  Nothing of size (n S + q)^2 is formed: Phi_w = QR,
+ * the Schur complement M of H^T H on the alpha block is the Gram matrix of the Kaufman Jacobian, factored in double.
+ * At the handle's current parameters (after vp_fit, vp_set_params, vp_set_params_with_basis or -- with the columns of the
+ * fitted point passed by vp_set_params_with_basis -- vp_fit_end); descriptor and caller-evaluated handles alike.
+ *   cov_alpha_out       [B][q][q]       handle dtype   sigma^2 M^-1 = Cov(alpha, alpha)
+ *   reduced_chi2_out    [B] f64                        sum_s ||r_w,s||^2 / (m S - n S - q)
+ *   coef_cov_out        [B][S][n][n] or NULL           Cov(c_s, c_s)
+ *   coef_alpha_cov_out  [B][S][n][q] or NULL           Cov(c_s, alpha)  (row a = coefficient a)
+ *   conf_sigma_out      [B][S][m] or NULL              sqrt(j_{s,i}^T Cov j_{s,i}) with the UNweighted rows: multiply by
+ *                                                      t_ppf((p+1)/2, m S - n S - q) for the confidence band radius
+ *   status              [B] or NULL                    0 ok; 4 = Underdetermined / MatrixInversion of the stacked problem
+ *                                                      (m S <= n S + q, a zero / non-finite pivot of R or of M, or an
+ *                                                      evaluation that was not ok); its outputs are NaN
+ * The cross blocks Cov(c_s, c_t), s != t, are not produced.  With S == 1 the outputs are vp_statistics' blocks.
+ * Errors: VP_ERR_INVALID -- no parameters set yet, a null cov_alpha_out / reduced_chi2_out, or (caller-evaluated handle)
+ * no Phi / dPhi at the current parameters; VP_ERR_UNSUPPORTED -- right-hand sides sharded over ranks
+ * (vp_set_rhs_allreduce: the statistics need sums over ALL right-hand sides, a cross-rank reduction this entry does not
+ * make), or a shape beyond n <= 8, q <= 8, n_pairs <= 16.
+ */
+int vp_global_statistics(vp_batch *h, void *cov_alpha_out, double *reduced_chi2_out, void *coef_cov_out,
+                         void *coef_alpha_cov_out, void *conf_sigma_out, int32_t *status);
 
 /*
  * Local batch aggregates for the multi-GPU cost reduction:

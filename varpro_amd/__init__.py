@@ -16,7 +16,7 @@ from .pipeline import FitPipeline  # noqa: F401
 from .model import (ClosureModel, ExternalModel, ModelBuildError, ModelError, SeparableModel,  # noqa: F401
                     SeparableModelBuilder, basis, multi_exponential_model)
 from .problem import SeparableProblem, SeparableProblemBuilder, SeparableProblemBuilderError  # noqa: F401
-from .solver import (FitError, FitResult, FitStatistics, LevMarSolver, MinimizationReport,  # noqa: F401
+from .solver import (FitError, FitResult, FitStatistics, GlobalFitStatistics, LevMarSolver, MinimizationReport,  # noqa: F401
                      TerminationReason)  # noqa: F401
 
 __version__ = "0.1.0"

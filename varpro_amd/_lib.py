@@ -48,7 +48,7 @@ ABI_SYMBOLS = [
     "vp_best_fit", "vp_statistics", "vp_summary", "vp_summary_device", "vp_global_fit_condition", "vp_set_rhs_allreduce", "vp_set_fit_kernel", "vp_set_timing", "vp_last_kernel_ms", "vp_synchronize", "vp_last_error",
     "vp_last_error_detail", "vp_version", "vp_device_count",
     "vp_batch_create_external", "vp_set_params_with_basis", "vp_jacobian_with_derivatives", "vp_evaluate_with_basis",
-    "vp_reduce_cost", "vp_fit_begin", "vp_fit_step_with_basis", "vp_fit_end", "vp_fit_active_set",
+    "vp_reduce_cost", "vp_fit_begin", "vp_fit_step_with_basis", "vp_fit_end", "vp_fit_active_set", "vp_global_statistics",
 ]
 
 
@@ -140,6 +140,7 @@ def load():
     lib.vp_debug_lmpar_gram.argtypes = [C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     lib.vp_debug_set_refit.argtypes = [vp, C.c_int]
     lib.vp_statistics.argtypes = [vp, vp, vp, vp, vp]
+    lib.vp_global_statistics.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.vp_summary.argtypes = [vp, dp]
     lib.vp_summary_device.argtypes = [vp, vp]
     lib.vp_global_fit_condition.argtypes = [vp, vp]

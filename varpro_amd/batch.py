@@ -541,6 +541,24 @@ class BatchProblem:
         return dict(cov=cov, reduced_chi2=chi2, conf_sigma=sig, status=st, dof=self.m - k)
 
     @_device_entry
+    def global_statistics(self, want_coef_cov=True, want_confidence_sigma=False):
+        """Fit statistics of a global fit (any S >= 1; vp_global_statistics): FitStatistics::try_calculate on the stacked
+        single-RHS problem (m S observations, parameters [c_1 .. c_S, alpha]) -> dict(cov_alpha (B,q,q), reduced_chi2 (B,),
+        coef_cov (B,S,n,n) and coef_alpha_cov (B,S,n,q) or None, conf_sigma (B,S,m) or None, status (B,),
+        dof = m S - n S - q).  The cross blocks Cov(c_s, c_t), s != t, are not produced."""
+        B, S, n, q, m = self.B, self.S, self.n, self.q, self.m
+        cov = self._empty((B, q, q))
+        chi2 = self._empty((B,), np.float64)
+        cc = self._empty((B, S, n, n)) if want_coef_cov else None
+        ca = self._empty((B, S, n, q)) if want_coef_cov else None
+        sig = self._empty((B, S, m)) if want_confidence_sigma else None
+        st = self._empty((B,), np.int32)
+        check(self.lib.vp_global_statistics(self._h, self._ptr(cov), self._ptr(chi2), self._ptr(cc), self._ptr(ca),
+                                            self._ptr(sig), self._ptr(st)))
+        return dict(cov_alpha=cov, reduced_chi2=chi2, coef_cov=cc, coef_alpha_cov=ca, conf_sigma=sig, status=st,
+                    dof=m * S - n * S - q)
+
+    @_device_entry
     def set_observations(self, Y):
         """replace the data of this handle by another batch of the same shape (vp_set_observations): the next frame
         of a stream of same-shaped problems without re-allocating the device state"""

@@ -372,6 +372,41 @@ class BatchProblem {
         check(vp_statistics(h_, s.covariance.data(), s.reduced_chi2.data(), s.conf_sigma.data(), s.status.data()));
         return s;
     }
+    // statistics of a GLOBAL fit (any S): FitStatistics::try_calculate of the stacked problem, parameters [c_1 .. c_S, alpha]
+    // (vp_global_statistics; the cross blocks Cov(c_s, c_t), s != t, are not produced)
+    struct GlobalStatistics {
+        std::vector<double> cov_alpha;      // [B][q][q]
+        std::vector<double> reduced_chi2;   // [B]
+        std::vector<double> coef_cov;       // [B][S][n][n]
+        std::vector<double> coef_alpha_cov; // [B][S][n][q]
+        std::vector<double> conf_sigma;     // [B][S][m] (empty unless asked for)
+        std::vector<int32_t> status;        // [B]  0 ok, 4 = Underdetermined / MatrixInversion of the stacked problem
+        int64_t m = 0, S = 1, dof = 0;
+        // the Student-t scaled band of right-hand side s of problem b (src/statistics/mod.rs:271-304, stacked dof)
+        std::vector<double> confidence_band_radius(int64_t b, int64_t s, double probability) const {
+            if (!(probability > 0.0 && probability < 1.0)) throw std::invalid_argument("probability must be in (0,1)");
+            if (conf_sigma.empty()) throw std::logic_error("global_statistics(true) computes the band");
+            const double tq = student_t_quantile(0.5 * (1.0 + probability), (double)dof);
+            std::vector<double> r((size_t)m);
+            for (int64_t i = 0; i < m; ++i) r[(size_t)i] = tq * conf_sigma[(size_t)((b * S + s) * m + i)];
+            return r;
+        }
+    };
+    GlobalStatistics global_statistics(bool want_confidence_sigma = false) const {
+        GlobalStatistics g;
+        g.cov_alpha.resize((size_t)(B * q * q));
+        g.reduced_chi2.resize((size_t)B);
+        g.coef_cov.resize((size_t)(B * S * n * n));
+        g.coef_alpha_cov.resize((size_t)(B * S * n * q));
+        if (want_confidence_sigma) g.conf_sigma.resize((size_t)(B * S * m));
+        g.status.resize((size_t)B);
+        g.m = m;
+        g.S = S;
+        g.dof = m * S - (int64_t)n * S - q;
+        check(vp_global_statistics(h_, g.cov_alpha.data(), g.reduced_chi2.data(), g.coef_cov.data(), g.coef_alpha_cov.data(),
+                                   want_confidence_sigma ? g.conf_sigma.data() : nullptr, g.status.data()));
+        return g;
+    }
     // one global fit sharded by right-hand sides over ranks: `fn` sums `count` device doubles over all ranks on
     // the given HIP stream (ncclAllReduce on RCCL); see include/varpro_hip.h
     void set_rhs_allreduce(vp_allreduce_fn fn, void *user, int64_t global_rhs_count) {

@@ -17,6 +17,7 @@
 #include "vp_registry.hpp"
 #include "vp_extfit_api.hpp"
 #include "vp_mrhs.hpp"
+#include "vp_gstats.hpp"
 
 using namespace vp;
 
@@ -1959,6 +1960,131 @@ int vp_statistics(vp_batch *h, void *cov_out, double *reduced_chi2_out, void *co
     }
     if (st_tmp) (void)hipFree(st_tmp);
     if (rc != VP_ERR_OK) return fail(rc, "statistics kernel failed");
+    return VP_ERR_OK;
+}
+
+// == FitStatistics::try_calculate on the stacked single-RHS equivalent of a global fit (vp_gstats.hpp).  Problems go in
+// chunks whose workspace (basis columns + the kernels' row workspaces) stays within kGsWsBytes.
+int vp_global_statistics(vp_batch *h, void *cov_alpha_out, double *reduced_chi2_out, void *coef_cov_out,
+                         void *coef_alpha_cov_out, void *conf_sigma_out, int32_t *status) {
+    VP_ENTER(h);
+    if (!h->have_params) return fail(VP_ERR_INVALID, "no parameters set yet");
+    if (h->rhs_allreduce)
+        return fail(VP_ERR_UNSUPPORTED, "global fit statistics of right-hand sides sharded over ranks (vp_set_rhs_allreduce) "
+                                        "need a cross-rank reduction vp_global_statistics does not make");
+    if (!cov_alpha_out || !reduced_chi2_out) return fail(VP_ERR_INVALID, "null output");
+    if (h->external && !h->ext_phi)
+        return fail(VP_ERR_INVALID, "global fit statistics need the columns at the current parameters (vp_set_params_with_basis "
+                                    "with Phi and dPhi)");
+    if (h->external && h->ext_np > 0 && !h->ext_dphi)
+        return fail(VP_ERR_INVALID, "global fit statistics need the derivative columns at the current parameters "
+                                    "(vp_set_params_with_basis with dPhi)");
+    if (h->n > VP_MAX_BASIS || h->q > VP_MAX_PARAMS || h->p > VP_MAX_PAIRS || h->S > 0x7fffffff)
+        return fail(VP_ERR_UNSUPPORTED, "global fit statistics: shape out of range");
+    GStatsParams gp;
+    std::memset(&gp, 0, sizeof(gp));
+    gp.dtype = h->dtype;
+    gp.n = h->n;
+    gp.q = h->q;
+    if (h->external) {
+        gp.P = h->ext_np;
+        for (int i = 0; i < h->ext_np; ++i) {
+            gp.pb[i] = h->ext_pb[i];
+            gp.pp[i] = h->ext_pp[i];
+        }
+    } else { // the descriptor's pairs in vp_basis' order (basis-major, argument slot within a basis)
+        for (int j = 0; j < h->n; ++j)
+            for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k)
+                if (h->model.param[j][k] >= 0) {
+                    gp.pb[gp.P] = j;
+                    gp.pp[gp.P] = h->model.param[j][k];
+                    ++gp.P;
+                }
+    }
+    const size_t ts = tsize(h->dtype);
+    const int64_t m = h->m, S = h->S, B = h->B, n = h->n, q = h->q, P = gp.P;
+    gp.m = (int)m;
+    gp.rows = h->external ? (int)(h->m_user ? h->m_user : m) : (int)m;
+    gp.m_dof = h->m_user ? h->m_user : m;
+    gp.S = (int)S;
+    gp.w_stride = (h->flags & VP_FLAG_W_PER_PROBLEM) ? m : 0;
+    gp.stream = h->stream;
+    const bool band = conf_sigma_out != nullptr;
+    // bytes of one problem's workspace: basis columns (descriptor handles) + prep columns + row constants + the small record
+    const size_t per_b = (h->external ? 0 : (size_t)(n + P) * m * ts) + (size_t)(n + P) * m * 8 +
+                         (band ? (size_t)(1 + n * (n + 1) / 2) * m * 8 : 0) + gs::kGsSmall * 8;
+    constexpr size_t kGsWsBytes = (size_t)1 << 30;
+    const int64_t bc = std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)(kGsWsBytes / per_b)));
+    OutBuf cov, chi2, cc, ca;
+    RowOut sig;
+    if (int rc = cov.init(h, cov_alpha_out, (size_t)B * q * q * ts)) return rc;
+    if (int rc = chi2.init(h, reduced_chi2_out, (size_t)B * sizeof(double))) return rc;
+    if (int rc = cc.init(h, coef_cov_out, (size_t)B * S * n * n * ts)) return rc;
+    if (int rc = ca.init(h, coef_alpha_cov_out, (size_t)B * S * n * q * ts)) return rc;
+    if (int rc = sig.init(h, conf_sigma_out, (size_t)B * S)) return rc;
+    struct DevMem { // freed on every path (hipFree synchronises)
+        void *p = nullptr;
+        ~DevMem() {
+            if (p) (void)hipFree(p);
+        }
+    } ws, st_tmp;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t sz_basis = h->external ? 0 : al((size_t)bc * (n + P) * m * ts), sz_cols = al((size_t)bc * (n + P) * m * 8),
+                 sz_rows = band ? al((size_t)bc * (1 + n * (n + 1) / 2) * m * 8) : 0, sz_small = (size_t)bc * gs::kGsSmall * 8;
+    VP_HIP(hipMalloc(&ws.p, sz_basis + sz_cols + sz_rows + sz_small));
+    int32_t *st_dev = status && device_ptrs(h) ? status : nullptr;
+    if (!st_dev) {
+        VP_HIP(hipMalloc(&st_tmp.p, (size_t)B * sizeof(int32_t)));
+        st_dev = (int32_t *)st_tmp.p;
+    }
+    char *wsb = (char *)ws.p;
+    void *basis_ws = h->external ? nullptr : wsb;
+    gp.ws_cols = (double *)(wsb + sz_basis);
+    gp.ws_rows = band ? (double *)(wsb + sz_basis + sz_cols) : nullptr;
+    gp.ws_small = (double *)(wsb + sz_basis + sz_cols + sz_rows);
+    const char *wdev = (const char *)h->d_w;
+    for (int64_t b0 = 0; b0 < B; b0 += bc) {
+        const int64_t nb = std::min<int64_t>(bc, B - b0);
+        if (h->external) {
+            gp.phi = (const char *)h->ext_phi + (size_t)b0 * n * gp.rows * ts;
+            gp.dphi = h->ext_dphi ? (const char *)h->ext_dphi + (size_t)b0 * P * gp.rows * ts : nullptr;
+        } else { // the unweighted columns of this chunk at the handle's parameters: the set's own vp_basis kernel
+            LaunchParams p;
+            fill_params(h, p);
+            p.B = nb;
+            p.alpha = (const char *)h->d_alpha + (size_t)b0 * q * ts;
+            p.t = (const char *)h->d_t + (size_t)b0 * p.t_stride * ts;
+            p.w = h->d_w ? wdev + (size_t)b0 * p.w_stride * ts : nullptr;
+            p.Phi_out = basis_ws;
+            p.dPhi_out = (char *)basis_ws + (size_t)nb * n * m * ts;
+            p.basis_flags = 0;
+            if (int rc = h->kern->basis(p)) return fail(rc, "basis kernel launch failed");
+            gp.phi = p.Phi_out;
+            gp.dphi = P > 0 ? p.dPhi_out : nullptr;
+        }
+        gp.B = nb;
+        gp.w = h->d_w ? wdev + (size_t)b0 * gp.w_stride * ts : nullptr;
+        gp.C = (const char *)h->d_C + (size_t)b0 * S * n * ts;
+        gp.cost = h->d_cost + b0;
+        gp.status_in = h->d_status + b0;
+        gp.cov_alpha = (char *)cov.dptr + (size_t)b0 * q * q * ts;
+        gp.chi2 = (double *)chi2.dptr + b0;
+        gp.coef_cov = cc.dptr ? (char *)cc.dptr + (size_t)b0 * S * n * n * ts : nullptr;
+        gp.coef_alpha_cov = ca.dptr ? (char *)ca.dptr + (size_t)b0 * S * n * q * ts : nullptr;
+        gp.band = sig.dptr ? (char *)sig.dptr + (size_t)b0 * S * m * ts : nullptr;
+        gp.status_out = st_dev + b0;
+        if (int rc = gstats_launch(gp)) return fail(rc, "global statistics kernels failed");
+    }
+    if (int rc = cov.finish(h)) return rc;
+    if (int rc = chi2.finish(h)) return rc;
+    if (int rc = cc.finish(h)) return rc;
+    if (int rc = ca.finish(h)) return rc;
+    if (int rc = sig.finish(h)) return rc;
+    if (status && !device_ptrs(h)) {
+        VP_HIP(hipMemcpyAsync(status, st_dev, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        VP_HIP(hipStreamSynchronize(h->stream));
+    }
+    if (device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream)); // (the workspace is freed on return)
     return VP_ERR_OK;
 }
 

@@ -105,6 +105,60 @@ class FitStatistics:
         return _st.t.ppf((probability + 1.0) / 2.0, self._dof) * self._sigma
 
 
+class GlobalFitStatistics:
+    """Statistics of a global fit (one alpha shared by S right-hand sides): ``FitStatistics::try_calculate``
+    (src/statistics/mod.rs:352-441) on the equivalent stacked single-RHS problem, whose parameters are
+    [c_1 .. c_S, alpha] and whose degrees of freedom are m S - n S - q (vp_global_statistics).  The cross blocks
+    Cov(c_s, c_t), s != t, are not produced."""
+
+    def __init__(self, cov_alpha, reduced_chi2, coef_cov, coef_alpha_cov, conf_sigma, dof):
+        self._cov_alpha = np.asarray(cov_alpha)
+        self._chi2 = float(reduced_chi2)
+        self._coef_cov = np.asarray(coef_cov)              # (S, n, n)
+        self._coef_alpha_cov = np.asarray(coef_alpha_cov)  # (S, n, q)
+        self._sigma = np.asarray(conf_sigma)               # (S, m)
+        self._dof = int(dof)
+
+    def nonlinear_parameters_covariance_matrix(self):
+        """Cov(alpha, alpha), q x q"""
+        return self._cov_alpha
+
+    def nonlinear_parameters_correlation_matrix(self):
+        d = np.sqrt(np.diag(self._cov_alpha))
+        return self._cov_alpha / np.outer(d, d)
+
+    def nonlinear_parameters_variance(self):
+        return np.diag(self._cov_alpha).copy()
+
+    def linear_coefficients_covariance(self):
+        """Cov(c_s, c_s) for every right-hand side, (S, n, n)"""
+        return self._coef_cov
+
+    def linear_nonlinear_covariance(self):
+        """Cov(c_s, alpha) for every right-hand side, (S, n, q)"""
+        return self._coef_alpha_cov
+
+    def linear_coefficients_variance(self):
+        """(n, S): oriented like the coefficients of an MRHS problem"""
+        return np.ascontiguousarray(np.diagonal(self._coef_cov, axis1=1, axis2=2).T)
+
+    def reduced_chi2(self):
+        return self._chi2
+
+    def regression_standard_error(self):
+        return float(np.sqrt(self._chi2))
+
+    def degrees_of_freedom(self):
+        return self._dof
+
+    def confidence_band_radius(self, probability):
+        """(m, S): Student-t quantile at the stacked dof times the unscaled band (src/statistics/mod.rs:271-304)"""
+        if not (np.isfinite(probability) and 0.0 < probability < 1.0):
+            raise ValueError("probability must be in open interval (0.,1.)")
+        from scipy import stats as _st
+        return _st.t.ppf((probability + 1.0) / 2.0, self._dof) * np.ascontiguousarray(self._sigma.T)
+
+
 class FitError(RuntimeError):
     """the ``Err(FitResult)`` arm of ``LevMarSolver::fit`` (src/solvers/levmar/mod.rs:248-253)"""
 
@@ -149,4 +203,18 @@ class LevMarSolver:
             raise FitError(result)
         stats = FitStatistics(st["cov"][0], st["reduced_chi2"][0], problem.residuals(), st["conf_sigma"][0],
                               problem.n, problem.q, st["dof"])
+        return result, stats
+
+    def fit_with_global_statistics(self, problem):
+        """A global fit (``SeparableProblemBuilder.mrhs``) and its statistics (GlobalFitStatistics); raises FitError if
+        the fit or the statistics (underdetermined / singular stacked problem) fail"""
+        if not problem._mrhs:
+            raise ValueError("fit_with_global_statistics needs a problem with multiple right hand sides "
+                             "(fit_with_statistics covers a single one)")
+        result = self.fit(problem)
+        st = problem._batch.global_statistics(want_coef_cov=True, want_confidence_sigma=True)
+        if int(st["status"][0]) != 0 or problem.linear_coefficients() is None:
+            raise FitError(result)
+        stats = GlobalFitStatistics(st["cov_alpha"][0], st["reduced_chi2"][0], st["coef_cov"][0], st["coef_alpha_cov"][0],
+                                    st["conf_sigma"][0], st["dof"])
         return result, stats
