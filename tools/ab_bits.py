@@ -1,9 +1,84 @@
 """Bit-level comparison of library builds: fits the bench's 65 536 headline problems (and 4 096 at m = 1000, the general-length
 slot kernel) with each library in its own process and prints a hash of (parameters, coefficients, reports).
-usage: python tools/ab_bits.py libA.so libB.so ..."""
-import hashlib, os, subprocess, sys
+--ext: the caller-evaluated family instead -- vp_evaluate_with_basis (r, J, C, cost, status) at a resident length, on four
+and eight waves per problem and streamed (m = 10 000), weighted and unweighted, and one stepped fit per protocol (eager,
+derivatives on accept) at a resident and a streamed length (parameters, coefficients, reports); with --time also the device
+time of every leg (torch events around back-to-back calls; the fit: its first step, and end to end with the columns
+recomputed by torch every step).  --rounds N alternates the libraries N times; --json writes every line's numbers.
+usage: python tools/ab_bits.py [--ext [--time] [--rounds N] [--json out.json]] libA.so libB.so ..."""
+import hashlib, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def sha(*arrays):
+    import numpy as np
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a).tobytes())
+    return h.hexdigest()[:16]
+
+
+def ext_child(timed):
+    import numpy as np, torch
+    import varpro_amd as vp
+    from varpro_amd import synth
+    dev = torch.device("cuda", 0)
+
+    def ms(fn, reps):
+        fn(); torch.cuda.synchronize()
+        ts = []
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps): fn()
+            e1.record(); torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) / reps)
+        return sorted(ts)[len(ts) // 2]
+
+    def problem(B, m, weighted):
+        d = synth.double_exp_batch(B, m=m, noise=1e-3)
+        x = torch.from_numpy(np.asarray(d["x"], dtype=np.float64).reshape(-1)[:m]).to(dev)
+        w = (1.0 + 0.5 * torch.cos(0.01 * torch.arange(m, dtype=torch.float64, device=dev))) if weighted else None
+        bp = vp.BatchProblem(vp.ExternalModel(3, 2, [(0, 0), (1, 1)]), torch.from_numpy(d["Y"]).to(dev), weights=w)
+
+        def columns(alpha, want=None):  # exp(-x/t1), exp(-x/t2), 1 and the two derivative columns
+            e = torch.exp(-x[None, None, :] / alpha[:, :, None])
+            return torch.cat([e, torch.ones_like(e[:, :1])], 1).contiguous(), (e * x[None, None, :] / alpha[:, :, None] ** 2).contiguous()
+        return bp, torch.from_numpy(d["tau_guess"]).to(dev), columns
+
+    # (evaluate legs: the bench's external_model shapes; the fit legs: external_fit's)
+    for name, B, m in (("resident", 65536, 1024), ("w4", 8192, 4096), ("w8", 8192, 8192), ("streamed", 4096, 10000)):
+        for weighted in (False, True):
+            bp, g, columns = problem(B, m, weighted)
+            Phi, dPhi = columns(g)
+            o = bp.evaluate_with_basis(g, Phi, dPhi)
+            t = " ms %.4f" % ms(lambda: bp.evaluate_with_basis(g, Phi, dPhi), 10) if timed else ""
+            print("LEG evaluate_%s_%s sha %s%s" % (name, "weighted" if weighted else "plain", sha(o["r"], o["J"], o["C"], o["cost"], o["status"]), t))
+            bp.close()
+            del bp, Phi, dPhi, o
+    for name, B, m in (("resident", 65536, 1024), ("streamed", 4096, 10000)):
+        for lazy in (False, True):
+            bp, g, columns = problem(B, m, False)
+            a, C, rep, steps = bp.fit_with_model(columns, g, derivatives_on_accept=lazy)
+            r = bp.report_to_numpy(rep)
+            t = ""
+            if timed:
+                Phi, dPhi = columns(g)
+
+                def first_step():
+                    bp.fit_begin(g, derivatives_on_accept=lazy)
+                    bp.fit_step_with_basis(Phi, dPhi, want_count=False)
+                t = " ms %.4f ms_end_to_end %.3f" % (ms(first_step, 5), ms(lambda: bp.fit_with_model(columns, g, derivatives_on_accept=lazy, check_every=4), 1))
+            print("LEG fit_%s_%s sha %s evals %d steps %d%s" % (name, "on_accept" if lazy else "eager", sha(a, C, r["n_evals"], r["objective"], r["termination"]),
+                                                               int(r["n_evals"].sum()), steps, t))
+            bp.close()
+            del bp
+
+
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
+    if "--ext" in sys.argv:
+        ext_child("--time" in sys.argv)
+        sys.exit(0)
     import numpy as np
     import varpro_amd as vp
     from varpro_amd import synth
@@ -13,14 +88,23 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
         bp = vp.BatchProblem(mdl, d["Y"], x=d["x"])
         if fg and hasattr(bp, "set_fit_kernel"): bp.set_fit_kernel(fg)
         a, C, rep = bp.fit(d["tau_guess"])
-        h = hashlib.sha256(np.ascontiguousarray(a).tobytes() + np.ascontiguousarray(C).tobytes() + np.ascontiguousarray(rep["n_evals"]).tobytes()
-                           + np.ascontiguousarray(rep["objective"]).tobytes() + np.ascontiguousarray(rep["termination"]).tobytes()).hexdigest()[:16]
-        print("B=%d m=%d: evals %d  sha %s" % (B, m, int(rep["n_evals"].sum()), h))
+        print("B=%d m=%d: evals %d  sha %s" % (B, m, int(rep["n_evals"].sum()), sha(a, C, rep["n_evals"], rep["objective"], rep["termination"])))
         bp.close()
     sys.exit(0)
-for lib in [a for a in sys.argv[1:] if a.endswith(".so")]:
-    o = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=dict(os.environ, VARPRO_HIP_LIBRARY=os.path.abspath(lib), PYTHONPATH=ROOT),
-                       capture_output=True, text=True, cwd=ROOT)
-    for ln in o.stdout.splitlines():
-        if ln.startswith("B="): print("%-28s %s" % (os.path.basename(lib), ln))
-    if o.returncode != 0: print(os.path.basename(lib), "FAILED", o.stderr[-600:])
+flags = [a for a in sys.argv[1:] if a in ("--ext", "--time")]
+rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 1
+record = []
+for rnd in range(rounds):
+    for lib in [a for a in sys.argv[1:] if a.endswith(".so")]:
+        o = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + flags, env=dict(os.environ, VARPRO_HIP_LIBRARY=os.path.abspath(lib), PYTHONPATH=ROOT),
+                           capture_output=True, text=True, cwd=ROOT, timeout=420)
+        for ln in o.stdout.splitlines():
+            if ln.startswith("B=") or ln.startswith("LEG "):
+                print("%-28s %s" % (os.path.basename(lib), ln), flush=True)
+                w = ln.split()
+                if w[0] == "LEG": record.append(dict({"library": os.path.basename(lib), "round": rnd, "leg": w[1]},
+                                   **{w[i]: (w[i + 1] if w[i] == "sha" else float(w[i + 1])) for i in range(2, len(w) - 1, 2)}))
+        if o.returncode != 0:
+            print(os.path.basename(lib), "FAILED", o.stderr[-600:])
+            sys.exit(1)  # (nothing more is started on the device after a failed child)
+if "--json" in sys.argv: json.dump(record, open(sys.argv[sys.argv.index("--json") + 1], "w"), indent=1)

@@ -53,52 +53,37 @@ enum { EXTFIT_PH_EVAL = 0, EXTFIT_PH_JAC = 1 };
 // The per-problem state, structure-of-arrays: field f of problem b is base[f * B + b] (the LM kernel's lane b reads and
 // writes it coalesced; the evaluation kernel's wave b touches a handful of scalars).  Q parameters, up to VP_MAX_BASIS
 // coefficients.
-template <int Q> struct ExtFitLayout {
-    // fields of the problem's scalar type
-    static constexpr int X = 0, XT = X + Q, DIAG = XT + Q, QTF = DIAG + Q, ACN = QTF + Q, RJ = ACN + Q, SC = RJ + Q * Q;
-    // SC + {0 fnorm, 1 delta, 2 par, 3 xnorm, 4 gnorm, 5 pnorm, 6 prered, 7 dirder, 8 objective}
-    static constexpr int CBEST = SC + 9, C_FN = CBEST + VP_MAX_BASIS, C_C = C_FN + 1, C_RJ = C_C + VP_MAX_BASIS;
-    static constexpr int C_ACN = C_RJ + Q * Q, C_QTF = C_ACN + Q, NT = C_QTF + Q;
-    // 32-bit fields
-    static constexpr int IPVT = 0, FIRST = IPVT + Q, FIRST_TR = FIRST + 1, FIRST_UP = FIRST_TR + 1, NFEV = FIRST_UP + 1;
-    static constexpr int TERM = NFEV + 1, STATUS = TERM + 1, WANT = STATUS + 1, PHASE = WANT + 1, C_OK = PHASE + 1;
-    static constexpr int C_HASJ = C_OK + 1, C_IPVT = C_HASJ + 1, NI = C_IPVT + Q;
-    // bytes per problem (+ 8 per handle for the alignment of the 32-bit block: added by the host)
-    static constexpr size_t bytes(size_t tsize) { return (size_t)NT * tsize + (size_t)NI * 4; }
-};
-// The same offsets for a RUN-TIME parameter count: the generic step kernel (vp_gen_extfit.hpp: any (n, pairs, q) the header
-// admits, any number of right-hand sides) is compiled once and writes the candidate slot of whichever ExtFitLayout<Q> the LM
-// kernel of the handle's q reads.
+// The field offsets are one set of formulas, extfit_offsets(Q): a compile-time Q reads them as ExtFitLayout<Q>'s constants,
+// the generic step kernel (vp_gen_extfit.hpp: any (n, pairs, q) the header admits, any number of right-hand sides; compiled
+// once) calls it with the handle's q and writes the candidate slot of whichever ExtFitLayout<Q> the LM kernel reads.
 struct ExtFitOffsets {
-    int C_FN, C_C, C_RJ, C_ACN, C_QTF, NT;
-    int TERM, WANT, C_OK, C_HASJ, C_IPVT;
+    // fields of the problem's scalar type
+    int X, XT, DIAG, QTF, ACN, RJ;
+    int SC; // SC + {0 fnorm, 1 delta, 2 par, 3 xnorm, 4 gnorm, 5 pnorm, 6 prered, 7 dirder, 8 objective}
+    int CBEST, C_FN, C_C, C_RJ, C_ACN, C_QTF, NT;
+    // 32-bit fields
+    int IPVT, FIRST, FIRST_TR, FIRST_UP, NFEV, TERM, STATUS, WANT, PHASE, C_OK, C_HASJ, C_IPVT, NI;
 };
 __host__ __device__ constexpr ExtFitOffsets extfit_offsets(const int Q) {
     ExtFitOffsets o{};
-    const int SC = 5 * Q + Q * Q, CBEST = SC + 9;
-    o.C_FN = CBEST + VP_MAX_BASIS;
-    o.C_C = o.C_FN + 1;
-    o.C_RJ = o.C_C + VP_MAX_BASIS;
-    o.C_ACN = o.C_RJ + Q * Q;
-    o.C_QTF = o.C_ACN + Q;
-    o.NT = o.C_QTF + Q;
-    const int NFEV = Q + 3;
-    o.TERM = NFEV + 1;
-    o.WANT = o.TERM + 2;
-    o.C_OK = o.WANT + 2;
-    o.C_HASJ = o.C_OK + 1;
-    o.C_IPVT = o.C_HASJ + 1;
+    o.X = 0; o.XT = o.X + Q; o.DIAG = o.XT + Q; o.QTF = o.DIAG + Q; o.ACN = o.QTF + Q; o.RJ = o.ACN + Q; o.SC = o.RJ + Q * Q;
+    o.CBEST = o.SC + 9; o.C_FN = o.CBEST + VP_MAX_BASIS; o.C_C = o.C_FN + 1; o.C_RJ = o.C_C + VP_MAX_BASIS;
+    o.C_ACN = o.C_RJ + Q * Q; o.C_QTF = o.C_ACN + Q; o.NT = o.C_QTF + Q;
+    o.IPVT = 0; o.FIRST = o.IPVT + Q; o.FIRST_TR = o.FIRST + 1; o.FIRST_UP = o.FIRST_TR + 1; o.NFEV = o.FIRST_UP + 1;
+    o.TERM = o.NFEV + 1; o.STATUS = o.TERM + 1; o.WANT = o.STATUS + 1; o.PHASE = o.WANT + 1; o.C_OK = o.PHASE + 1;
+    o.C_HASJ = o.C_OK + 1; o.C_IPVT = o.C_HASJ + 1; o.NI = o.C_IPVT + Q;
     return o;
 }
-template <int Q> constexpr bool extfit_offsets_match() {
-    using F = ExtFitLayout<Q>;
-    constexpr ExtFitOffsets o = extfit_offsets(Q);
-    return o.C_FN == F::C_FN && o.C_C == F::C_C && o.C_RJ == F::C_RJ && o.C_ACN == F::C_ACN && o.C_QTF == F::C_QTF && o.NT == F::NT &&
-           o.TERM == F::TERM && o.WANT == F::WANT && o.C_OK == F::C_OK && o.C_HASJ == F::C_HASJ && o.C_IPVT == F::C_IPVT;
-}
-static_assert(extfit_offsets_match<1>() && extfit_offsets_match<2>() && extfit_offsets_match<3>() && extfit_offsets_match<4>() &&
-                  extfit_offsets_match<5>() && extfit_offsets_match<6>() && extfit_offsets_match<7>() && extfit_offsets_match<8>(),
-              "extfit_offsets must mirror ExtFitLayout");
+template <int Q> struct ExtFitLayout {
+    static constexpr ExtFitOffsets O = extfit_offsets(Q);
+    static constexpr int X = O.X, XT = O.XT, DIAG = O.DIAG, QTF = O.QTF, ACN = O.ACN, RJ = O.RJ, SC = O.SC;
+    static constexpr int CBEST = O.CBEST, C_FN = O.C_FN, C_C = O.C_C, C_RJ = O.C_RJ, C_ACN = O.C_ACN, C_QTF = O.C_QTF, NT = O.NT;
+    static constexpr int IPVT = O.IPVT, FIRST = O.FIRST, FIRST_TR = O.FIRST_TR, FIRST_UP = O.FIRST_UP, NFEV = O.NFEV;
+    static constexpr int TERM = O.TERM, STATUS = O.STATUS, WANT = O.WANT, PHASE = O.PHASE, C_OK = O.C_OK;
+    static constexpr int C_HASJ = O.C_HASJ, C_IPVT = O.C_IPVT, NI = O.NI;
+    // bytes per problem (+ 8 per handle for the alignment of the 32-bit block: added by the host)
+    static constexpr size_t bytes(size_t tsize) { return (size_t)NT * tsize + (size_t)NI * 4; }
+};
 
 // the 32-bit fields start behind the NT * B scalars, 8-byte aligned
 template <typename T> __host__ __device__ inline int32_t *extfit_ints_rt(void *state, int64_t B, const int NT) {
