@@ -47,6 +47,22 @@ int fail(int code, const std::string &msg, int detail = 0) {
 
 inline size_t tsize(int dtype) { return dtype == VP_F64 ? 8 : 4; }
 
+// scoped device memory: every temporary of an entry point.  Freed at the end of its scope -- hipFree synchronises the
+// device, so WHERE that scope ends relative to the work around it is part of an entry point's behaviour
+struct DevMem {
+    void *p = nullptr;
+    DevMem() = default;
+    DevMem(const DevMem &) = delete;
+    DevMem &operator=(const DevMem &) = delete;
+    int alloc(size_t bytes) {
+        VP_HIP(hipMalloc(&p, bytes));
+        return 0;
+    }
+    ~DevMem() {
+        if (p) (void)hipFree(p);
+    }
+};
+
 // ---- small utility kernels (dtype-generic plumbing, not the hot path) ------------------------------
 // (Y and Yw may be the same buffer -- vp_set_observations stages host data through Yw -- hence no __restrict__ on them:
 // every element is read and written by the same thread)
@@ -169,95 +185,150 @@ template <typename T> __global__ void grid_check_kernel(const T *t, int m, int64
 } // namespace
 
 // ---- the handle ------------------------------------------------------------------------------------
-struct vp_batch {
-    vp_model_desc model;
-    int dtype;
-    int64_t m, S, B;
-    int n, q, p;
-    int flags;
-    int device;
-    double eps;
-    hipStream_t stream;
-    bool own_stream;
-    const KernelEntry *kern;
+// The captured graphs of the global fit (mrhs_fit_specialised) and the policy that decides their length.  The whole fit
+// is ONE graph (`head`: init, `len` iterations, finish); a fit that outlasts it continues with replays of `tail`
+// (kTailIters further iterations + finish).  Both hold the LM options by value.
+struct MrhsGraphs {
+    static constexpr int kFirstIters = 12, kTailIters = 12, kMinIters = 6, kMaxIters = 24;
+    hipGraphExec_t head = nullptr, tail = nullptr;
+    hipStream_t cap_stream = nullptr; // capture happens on a private stream: the handle's may be the null stream
+    vp_lm_opts opts = {};             // the options both graphs were captured with
+    int len = 0;                      // LM iterations `head` holds
+    int next_len = 0;                 // ... and what the next capture should hold (0: no fit yet)
+    int prev_nfev = 0;                // largest evaluation count of the previous fit, and for how many fits in a row it has
+    int same_count = 0;               // been the same: a stream of fits of one length runs a graph WITHOUT the spare iteration
+    bool failed = false;              // a capture failed: plain launches for the rest of the handle's life
+
+    bool opts_changed(const vp_lm_opts &o) const { return !head || std::memcmp(&opts, &o, sizeof(o)) != 0; }
+    int wanted_len() const { return next_len > 0 ? next_len : kFirstIters; }
+    // Re-capture with hysteresis: on streaming data the longest fit moves by +-1 evaluation from one call to the next, and a
+    // capture + instantiation costs as much as the fit it speeds up.  The head is re-captured when the options changed, when
+    // the wanted length EXCEEDS the captured one (every further iteration would cost a replay of the tail graph) or falls
+    // short of it by 4 or more (each idle iteration is two empty launches, ~10 us); the tail graph does not depend on the
+    // length and is only re-captured with the options.
+    // (A handle whose last VP_MRHS_EXACT_AFTER + 1 fits took the same number of evaluations drops the spare iteration -- two
+    // empty launches, ~10 us of a 0.7 ms fit: the wanted length is then exact and the head is re-captured ONCE, down to that
+    // length.  The exact length only ever SHRINKS the graph: a stream whose longest fit moves by +-1 every few calls
+    // (A A A B A A A B) never reaches the run length, and after a miss the spare-iteration rule decides alone -- no
+    // recapture per fluctuation.)
+    bool head_stale(const vp_lm_opts &o) const {
+        const int want = wanted_len();
+        const bool exact = same_count >= VP_MRHS_EXACT_AFTER;
+        return opts_changed(o) || want > len || want + 4 <= len || (exact && want < len);
+    }
+    // after a graph fit whose longest problem took nfev_max evaluations: the next capture holds as many iterations, plus
+    // one spare unless the run of equal fits is long enough
+    void observe(int nfev_max) {
+        same_count = (nfev_max == prev_nfev) ? same_count + 1 : 0;
+        prev_nfev = nfev_max;
+        const int want = nfev_max + (same_count >= VP_MRHS_EXACT_AFTER ? 0 : 1);
+        next_len = want < kMinIters ? kMinIters : (want > kMaxIters ? kMaxIters : want);
+    }
+    void drop() {
+        if (head) (void)hipGraphExecDestroy(head);
+        if (tail) (void)hipGraphExecDestroy(tail);
+        head = tail = nullptr;
+    }
+};
+
+// (hidden: the members below are this file's business, the library exports the C functions only)
+struct __attribute__((visibility("hidden"))) vp_batch {
+    vp_model_desc model = {};
+    int dtype = 0;
+    int64_t m = 0, S = 0, B = 0;
+    int n = 0, q = 0, p = 0;
+    int flags = 0;
+    int device = 0;
+    double eps = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    const KernelEntry *kern = nullptr;
+    // Every device / pinned allocation of the handle is made through alloc / ensure / alloc_pinned and recorded here;
+    // vp_batch_destroy frees the lists.  The typed pointers below are views: two of them may name one allocation.
+    std::vector<void *> owned_dev, owned_pinned;
+    template <typename T> int alloc(T *&ptr, size_t bytes) {
+        void *mem = nullptr;
+        VP_HIP(hipMalloc(&mem, bytes));
+        if (mem) owned_dev.push_back(mem);
+        ptr = static_cast<T *>(mem);
+        return 0;
+    }
+    // lazily allocated buffers: at the first call that needs them, kept for the handle's life
+    template <typename T> int ensure(T *&ptr, size_t bytes) { return ptr ? 0 : alloc(ptr, bytes); }
+    template <typename T> int alloc_pinned(T *&ptr, size_t bytes, unsigned hip_flags) {
+        void *mem = nullptr;
+        VP_HIP(hipHostMalloc(&mem, bytes, hip_flags));
+        owned_pinned.push_back(mem);
+        ptr = static_cast<T *>(mem);
+        return 0;
+    }
     // device state (== SeparableProblem + CachedCalculations for the whole batch)
-    void *d_t, *d_w, *d_yw;
-    void *d_alpha;      // [B][q]
-    void *d_C;          // [B][S][n]
-    void *d_R;          // [B][S][m]  lazily allocated residual cache
-    double *d_cost_bs;  // [B*S]
-    int32_t *d_status_bs;
-    double *d_cost;     // [B]   (aliases d_cost_bs when S == 1)
-    int32_t *d_status;  // [B]
-    vp_report *d_report; // [B]
-    double *d_sum4;
-    bool grid_uniform; // every grid is t_0 + i*dt to rounding (grid_check_kernel): kernels may use the exp recurrence
-    bool have_params; // set_params/evaluate/fit has run
-    bool r_valid;     // d_R matches d_alpha
-    bool have_report;
+    void *d_t = nullptr, *d_w = nullptr, *d_yw = nullptr;
+    void *d_alpha = nullptr;          // [B][q]
+    void *d_C = nullptr;              // [B][S][n]
+    void *d_R = nullptr;              // [B][S][m]  lazily allocated residual cache
+    double *d_cost_bs = nullptr;      // [B*S]
+    int32_t *d_status_bs = nullptr;
+    double *d_cost = nullptr;         // [B]   (the per-(b,s) arrays themselves when S == 1)
+    int32_t *d_status = nullptr;      // [B]
+    vp_report *d_report = nullptr;    // [B]
+    double *d_sum4 = nullptr;
+    bool grid_uniform = false; // every grid is t_0 + i*dt to rounding (grid_check_kernel): kernels may use the exp recurrence
+    bool have_params = false;  // set_params/evaluate/fit has run
+    bool r_valid = false;      // d_R matches d_alpha
+    bool have_report = false;
     // timing
-    bool timing;
-    hipEvent_t ev0, ev1;
-    float last_ms[3];
-    // multiple-right-hand-side path (S > 1): factor/stream/LM-step kernels + their workspace
-    bool have_mrhs;
-    MrhsWs mrhs;
+    bool timing = false;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float last_ms[3] = {-1.f, -1.f, -1.f};
+    // multiple-right-hand-side path (S > 1): factor/stream/LM-step kernels + their workspace, and the captured graphs
+    bool have_mrhs = false;
+    MrhsWs mrhs = {};
+    MrhsGraphs graphs;
+    int32_t *h_nactive = nullptr;     // pinned, device-mapped: the active count as the graph's last kernel leaves it
+    int32_t *h_nactive_dev = nullptr; // its device address
+    MrhsIo *h_io = nullptr;           // pinned, device-mapped: the caller's arrays of the current vp_fit (device-pointer handles)
+    MrhsIo *h_io_dev = nullptr;
     // S-sharded global fits (vp_set_rhs_allreduce)
-    vp_allreduce_fn rhs_allreduce;
-    void *rhs_allreduce_user;
-    int64_t rhs_global; // right-hand sides of the whole problem
-    double *d_mrhs_tot; // [B][1 + n*n + p] totals of the reduced sums (all-reduced across ranks); generic kernels: [B][2 + q*q + q]
-    void *d_gen_lm;     // generic kernels, sharded right-hand sides: [B] LM state between the phases
-    int32_t *d_gen_nactive;
+    vp_allreduce_fn rhs_allreduce = nullptr;
+    void *rhs_allreduce_user = nullptr;
+    int64_t rhs_global = 0;        // right-hand sides of the whole problem
+    double *d_mrhs_tot = nullptr;  // [B][1 + n*n + p] totals of the reduced sums (all-reduced across ranks); generic kernels: [B][2 + q*q + q]
+    void *d_gen_lm = nullptr;      // generic kernels, sharded right-hand sides: [B] LM state between the phases
+    int32_t *d_gen_nactive = nullptr;
     // single-RHS fit kernel selection (vp_set_fit_kernel) and the slot kernel's problem queue
-    int fit_kernel;
-    int *d_queue;
-    int num_cus;
-    void *tmp_a, *tmp_b; // scratch allocations of vp_batch_create (freed by destroy if create fails half way)
-    void *d_gen_ws;      // generic fallback kernels: gen_blocks workspace slots of (n + 1 + p + q) columns x m
-    int gen_blocks;
-    // MRHS fit: a captured HIP graph of VP_MRHS_GRAPH_ITERS {factor, stream, LM step} iterations (replayed per batch
-    // of iterations: one graph launch instead of 3 x ITERS kernel launches), the options it was captured with
-    int64_t m_user;  // != 0: the caller's row count m < n; the handle works on m = n rows, the extra ones with zero weight
-    hipGraphExec_t mrhs_graph;
-    hipGraphExec_t mrhs_graph_tail; // 12 further iterations + finish, for a fit that outlasts mrhs_graph
+    int fit_kernel = 0;
+    int *d_queue = nullptr;
+    int num_cus = 0;
+    void *d_gen_ws = nullptr; // generic fallback kernels: gen_blocks workspace slots of (n + 1 + p + q) columns x m
+    int gen_blocks = 0;
+    int64_t m_user = 0; // != 0: the caller's row count m < n; the handle works on m = n rows, the extra ones with zero weight
     // caller-evaluated model (vp_batch_create_external): shape + dependency-pair table, and where the columns of the
     // current parameters live (the caller's device arrays, or this handle's staged copies on host-pointer handles)
-    bool external;
-    int ext_np;
-    int32_t ext_pb[VP_MAX_PAIRS], ext_pp[VP_MAX_PAIRS];
-    const void *ext_phi, *ext_dphi;
-    void *ext_phi_own, *ext_dphi_own;
-    int mrhs_graph_len;     // LM iterations mrhs_graph holds
-    int mrhs_graph_iters;   // ... and what the next capture should hold (evaluations of the previous fit + 1, >= 6)
-    int mrhs_prev_nfev;     // largest evaluation count of the previous fit, and for how many fits in a row it has been the
-    int mrhs_same_count;    // same: a stream of fits of one length runs a graph WITHOUT the spare iteration
-    int32_t *h_nactive;     // pinned, device-mapped: the active count as the graph's last kernel leaves it
-    int32_t *h_nactive_dev; // its device address
-    MrhsIo *h_io;           // pinned, device-mapped: the caller's arrays of the current vp_fit (whole-fit graph, device-pointer handles)
-    MrhsIo *h_io_dev;
-    vp_lm_opts mrhs_graph_opts;
-    hipStream_t cap_stream;
-    bool mrhs_graph_failed;
+    bool external = false;
+    int ext_np = 0;
+    int32_t ext_pb[VP_MAX_PAIRS] = {}, ext_pp[VP_MAX_PAIRS] = {};
+    const void *ext_phi = nullptr, *ext_dphi = nullptr;
+    void *ext_phi_own = nullptr, *ext_dphi_own = nullptr;
     // batched reverse-communication LM fit of a caller-evaluated model (vp_fit_begin / vp_fit_step_with_basis / vp_fit_end)
-    void *d_xf_state;       // [B] LM records of the step kernel
-    void *d_xf_trial;       // [B][q] trial points of the last step
-    int32_t *d_xf_want;     // [B] what every problem wants next
-    void *d_xf_ctrial;      // [B][S][n] coefficients of the trial point (S > 1: generic step)
-    int32_t *d_xf_active;   // [2][B] compacted indices of the still-active problems, written alternately by the LM kernel
-    int64_t xf_known_active; // the last active count the host read (an upper bound of the current one)
-    int32_t *d_xf_nactive;  // device counter of the last step
-    int32_t *h_xf_nactive;  // pinned host copy
-    bool xf_running;        // between vp_fit_begin and vp_fit_end
-    bool xf_init;           // the next step is the first
-    int xf_flags;
-    int64_t xf_steps;
-    vp_lm_opts xf_opts;
+    void *d_xf_state = nullptr;      // [B] LM records of the step kernel
+    void *d_xf_trial = nullptr;      // [B][q] trial points of the last step
+    int32_t *d_xf_want = nullptr;    // [B] what every problem wants next
+    void *d_xf_ctrial = nullptr;     // [B][S][n] coefficients of the trial point (S > 1: generic step)
+    int32_t *d_xf_active = nullptr;  // [2][B] compacted indices of the still-active problems, written alternately by the LM kernel
+    int64_t xf_known_active = 0;     // the last active count the host read (an upper bound of the current one)
+    int32_t *d_xf_nactive = nullptr; // device counter of the last step
+    int32_t *h_xf_nactive = nullptr; // pinned host copy
+    bool xf_running = false;         // between vp_fit_begin and vp_fit_end
+    bool xf_init = false;            // the next step is the first
+    int xf_flags = 0;
+    int64_t xf_steps = 0;
+    vp_lm_opts xf_opts = {};
     // flag-and-refit of single-RHS fits (vp_fit.hpp jac_not_finite; rescue_refit below)
-    int32_t *d_rescue;      // [2 + B]: two ping-pong counters + the flagged problems of the running fit
-    void *d_rescue_ws;      // kRescueBlocks workspace slots of the generic fit kernel
-    int rescue_slot;        // the counter the NEXT fit appends to
-    bool rescue_off;        // vp_debug / VP_NO_RESCUE=1: fits keep the kernels' own `Numerical` (what rounds 1-4 returned)
+    int32_t *d_rescue = nullptr; // [2 + B]: two ping-pong counters + the flagged problems of the running fit
+    void *d_rescue_ws = nullptr; // kRescueBlocks workspace slots of the generic fit kernel
+    int rescue_slot = 0;         // the counter the NEXT fit appends to
+    bool rescue_off = false;     // vp_debug_set_refit(h, 0): fits keep the kernels' own `Numerical`
 };
 
 namespace {
@@ -267,7 +338,7 @@ bool device_ptrs(const vp_batch *h) { return (h->flags & VP_FLAG_DEVICE_PTRS) !=
 // input staging: user pointer -> device pointer usable on h->stream
 struct InBuf {
     const void *dptr = nullptr;
-    void *tmp = nullptr;
+    DevMem tmp;
     int init(vp_batch *h, const void *user, size_t bytes) {
         if (!user) {
             dptr = nullptr;
@@ -277,22 +348,17 @@ struct InBuf {
             dptr = user;
             return 0;
         }
-        VP_HIP(hipMalloc(&tmp, bytes ? bytes : 1));
-        VP_HIP(hipMemcpyAsync(tmp, user, bytes, hipMemcpyHostToDevice, h->stream));
-        dptr = tmp;
+        if (int rc = tmp.alloc(bytes ? bytes : 1)) return rc;
+        VP_HIP(hipMemcpyAsync(tmp.p, user, bytes, hipMemcpyHostToDevice, h->stream));
+        dptr = tmp.p;
         return 0;
-    }
-    ~InBuf() {
-        if (tmp) {
-            (void)hipFree(tmp); // hipFree synchronises
-        }
     }
 };
 
 // output staging: kernels write to dptr; finish() lands the bytes in the user's buffer
 struct OutBuf {
     void *dptr = nullptr;
-    void *tmp = nullptr;
+    DevMem tmp;
     void *user = nullptr;
     size_t bytes = 0;
     int init(vp_batch *h, void *user_, size_t bytes_) {
@@ -303,19 +369,16 @@ struct OutBuf {
             dptr = user;
             return 0;
         }
-        VP_HIP(hipMalloc(&tmp, bytes ? bytes : 1));
-        dptr = tmp;
+        if (int rc = tmp.alloc(bytes ? bytes : 1)) return rc;
+        dptr = tmp.p;
         return 0;
     }
     int finish(vp_batch *h) {
-        if (tmp) {
-            VP_HIP(hipMemcpyAsync(user, tmp, bytes, hipMemcpyDeviceToHost, h->stream));
+        if (tmp.p) {
+            VP_HIP(hipMemcpyAsync(user, tmp.p, bytes, hipMemcpyDeviceToHost, h->stream));
             VP_HIP(hipStreamSynchronize(h->stream));
         }
         return 0;
-    }
-    ~OutBuf() {
-        if (tmp) (void)hipFree(tmp);
     }
 };
 
@@ -363,8 +426,12 @@ int copy_out_rows(vp_batch *h, void *user, const void *dev, size_t blocks) {
     const size_t ts = tsize(h->dtype);
     if (!h->m_user) return copy_out(h, user, dev, blocks * (size_t)h->m * ts);
     const size_t bytes = blocks * (size_t)h->m_user * ts;
-    void *packed = device_ptrs(h) ? user : nullptr;
-    if (!packed) VP_HIP(hipMalloc(&packed, bytes ? bytes : 1));
+    DevMem tmp; // host-pointer handles: the packed rows on their way to the caller's host array
+    void *packed = user;
+    if (!device_ptrs(h)) {
+        if (int rc = tmp.alloc(bytes ? bytes : 1)) return rc;
+        packed = tmp.p;
+    }
     const int wu = (int)(h->m_user * ts / 4), wp = (int)(h->m * ts / 4);
     const int64_t total = (int64_t)blocks * wu;
     hipLaunchKernelGGL(strip_rows_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65536)), dim3(256), 0, h->stream,
@@ -374,7 +441,6 @@ int copy_out_rows(vp_batch *h, void *user, const void *dev, size_t blocks) {
         e = hipMemcpyAsync(user, packed, bytes, hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     }
-    if (!device_ptrs(h)) (void)hipFree(packed); // the temporary of host-pointer handles, on every path
     if (e != hipSuccess) return fail(VP_ERR_HIP, std::string("copy_out_rows: ") + hipGetErrorString(e));
     return 0;
 }
@@ -383,7 +449,7 @@ int copy_out_rows(vp_batch *h, void *user, const void *dev, size_t blocks) {
 // private array of padded blocks, finish() strips it into the caller's
 struct RowOut {
     OutBuf buf;
-    void *pad = nullptr;
+    DevMem pad;
     void *user = nullptr;
     size_t blocks = 0;
     void *dptr = nullptr;
@@ -396,17 +462,14 @@ struct RowOut {
             return rc;
         }
         if (!user) return 0;
-        VP_HIP(hipMalloc(&pad, blocks * (size_t)h->m * tsize(h->dtype)));
-        dptr = pad;
+        if (int rc = pad.alloc(blocks * (size_t)h->m * tsize(h->dtype))) return rc;
+        dptr = pad.p;
         return 0;
     }
     int finish(vp_batch *h) {
         if (!h->m_user) return buf.finish(h);
         if (!user) return 0;
-        return copy_out_rows(h, user, pad, blocks);
-    }
-    ~RowOut() {
-        if (pad) (void)hipFree(pad);
+        return copy_out_rows(h, user, pad.p, blocks);
     }
 };
 
@@ -450,6 +513,44 @@ void fill_params(vp_batch *h, LaunchParams &p) {
     p.ext_rows = (int)(h->m_user ? h->m_user : h->m);
 }
 
+// the launch record of one step of the running reverse-communication fit (everything but where the trial points go)
+void fill_ext_params(vp_batch *h, ExtFitParams &p) {
+    std::memset(&p, 0, sizeof(p));
+    p.dtype = h->dtype;
+    p.n = h->n;
+    p.q = h->q;
+    p.np = h->ext_np;
+    p.m = h->m;
+    p.B = h->B;
+    p.phi = h->ext_phi;
+    p.dphi = h->ext_dphi;
+    p.w = h->d_w;
+    p.yw = h->d_yw;
+    p.w_stride = (h->flags & VP_FLAG_W_PER_PROBLEM) ? h->m : 0;
+    p.state = h->d_xf_state;
+    p.alpha0 = h->d_alpha;
+    p.alpha_best = h->d_alpha;
+    p.C_best = h->d_C;
+    p.cost = h->d_cost;
+    p.status = h->d_status;
+    p.report = h->d_report;
+    p.nactive = h->d_xf_nactive;
+    p.step = (int)(h->xf_steps & 1);
+    p.pb = h->ext_pb;
+    p.pp = h->ext_pp;
+    p.eps = h->eps;
+    p.opts = h->xf_opts;
+    p.init = h->xf_init ? 1 : 0;
+    p.lazy = (h->xf_flags & VP_FIT_DERIVATIVES_ON_ACCEPT) ? 1 : 0;
+    p.S = h->S;
+    p.gen_ws = h->d_gen_ws;
+    p.gen_blocks = h->gen_blocks;
+    p.C_trial = h->d_xf_ctrial;
+    p.active_lists = h->d_xf_active;
+    p.known_active = h->xf_known_active;
+    p.stream = h->stream;
+}
+
 struct Timer {
     vp_batch *h;
     int which;
@@ -476,21 +577,123 @@ int reduce_rhs(vp_batch *h, hipStream_t stream_override = nullptr, bool use_over
 }
 
 // workspace of the generic kernels (vp_generic.hpp): one slot of (n + 1 + p + q) columns per persistent workgroup; at most
-// 1024 workgroups and 4 GiB
-int ensure_gen_ws(vp_batch *h) {
-    if (h->d_gen_ws || !h->kern->uses_gen_ws) return 0;
-    const size_t slot = (size_t)(h->n + 1 + h->p + h->q) * (size_t)h->m * tsize(h->dtype);
-    int64_t blocks = std::min<int64_t>(h->B * h->S, 1024);
+// 1024 workgroups (never more than `work_items`) and 4 GiB
+size_t gen_slot_bytes(const vp_batch *h) { return (size_t)(h->n + 1 + h->p + h->q) * (size_t)h->m * tsize(h->dtype); }
+int alloc_gen_ws(vp_batch *h, int64_t work_items) {
+    if (h->d_gen_ws) return 0;
+    const size_t slot = gen_slot_bytes(h);
+    int64_t blocks = std::min<int64_t>(work_items, 1024);
     while (blocks > 1 && (size_t)blocks * slot > ((size_t)4 << 30)) blocks /= 2;
     h->gen_blocks = (int)blocks;
-    VP_HIP(hipMalloc(&h->d_gen_ws, (size_t)blocks * slot));
+    return h->alloc(h->d_gen_ws, (size_t)blocks * slot);
+}
+int ensure_gen_ws(vp_batch *h) { return h->kern->uses_gen_ws ? alloc_gen_ws(h, h->B * h->S) : 0; }
+
+int ensure_R(vp_batch *h) { return h->ensure(h->d_R, (size_t)h->B * h->S * h->m * tsize(h->dtype)); }
+
+// ---- the steps several entry points share ---------------------------------------------------------------------------
+// the caller's parameters (device or host array, by the handle's flags) -> d_alpha
+int upload_alpha(vp_batch *h, const void *alpha) {
+    VP_HIP(hipMemcpyAsync(h->d_alpha, alpha, (size_t)h->B * h->q * tsize(h->dtype),
+                          device_ptrs(h) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     return 0;
 }
 
-int ensure_R(vp_batch *h) {
-    if (!h->d_R) VP_HIP(hipMalloc(&h->d_R, (size_t)h->B * h->S * h->m * tsize(h->dtype)));
+vp_lm_opts opts_or_default(const vp_batch *h, const vp_lm_opts *opts) {
+    vp_lm_opts o;
+    if (opts) o = *opts;
+    else vp_lm_opts_default(&o, h->dtype);
+    return o;
+}
+
+// the handle's state after a completed fit: parameters and report are the fit's, the residual cache is not
+void after_fit(vp_batch *h) {
+    h->have_params = true;
+    h->r_valid = false;
+    h->have_report = true;
+}
+// ... and after anything that invalidates the cached evaluation / fit
+void invalidate(vp_batch *h) {
+    h->have_params = false;
+    h->r_valid = false;
+    h->have_report = false;
+}
+
+// a fit's results into the caller's arrays (each may be null)
+int copy_fit_out(vp_batch *h, void *alpha_out, void *C_out, vp_report *rep) {
+    const size_t ts = tsize(h->dtype);
+    if (int rc = copy_out(h, alpha_out, h->d_alpha, (size_t)h->B * h->q * ts)) return rc;
+    if (int rc = copy_out(h, C_out, h->d_C, (size_t)h->B * h->S * h->n * ts)) return rc;
+    return copy_out(h, rep, h->d_report, (size_t)h->B * sizeof(vp_report));
+}
+
+// the trace of a vp_fit_trace call: [B][trace_rows][q + 4] doubles, NaN-filled (rows never written read as NaN).
+// tr.dptr stays null when no trace is wanted
+int trace_begin(vp_batch *h, OutBuf &tr, double *trace_out, int trace_rows) {
+    if (!trace_out || trace_rows <= 0) return 0;
+    const size_t bytes = (size_t)h->B * (size_t)trace_rows * (h->q + 4) * sizeof(double);
+    if (int rc = tr.init(h, trace_out, bytes)) return rc;
+    VP_HIP(hipMemsetAsync(tr.dptr, 0xFF, bytes, h->stream));
     return 0;
 }
+void set_trace(LaunchParams &p, const OutBuf &tr, int trace_rows) {
+    if (!tr.dptr) return;
+    p.trace = (double *)tr.dptr;
+    p.trace_rows = trace_rows;
+}
+
+// Y_w = W * Y into d_yw (ysrc may be d_yw itself)
+int launch_weight_data(vp_batch *h, const void *ysrc) {
+    const int64_t total = h->B * h->S * h->m;
+    const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 65536);
+    const int64_t wstride = (h->flags & VP_FLAG_W_PER_PROBLEM) ? h->m : 0;
+    if (h->dtype == VP_F64)
+        hipLaunchKernelGGL(weight_data_kernel<double>, dim3(grid), dim3(256), 0, h->stream, (const double *)ysrc,
+                           (const double *)h->d_w, (double *)h->d_yw, (int)h->m, h->S, wstride, total);
+    else
+        hipLaunchKernelGGL(weight_data_kernel<float>, dim3(grid), dim3(256), 0, h->stream, (const float *)ysrc,
+                           (const float *)h->d_w, (float *)h->d_yw, (int)h->m, h->S, wstride, total);
+    VP_HIP(hipGetLastError());
+    return 0;
+}
+
+// {sum cost, #successful, #failed, sum n_evals} of the last fit into four doubles of device memory
+int launch_summary(vp_batch *h, double *dev_out4) {
+    VP_HIP(hipMemsetAsync(dev_out4, 0, 4 * sizeof(double), h->stream));
+    const unsigned grid = (unsigned)std::min<int64_t>((h->B + 255) / 256, 1024);
+    hipLaunchKernelGGL(summary_kernel, dim3(grid), dim3(256), 0, h->stream, h->d_report, h->B, dev_out4);
+    VP_HIP(hipGetLastError());
+    return 0;
+}
+
+// the per-problem status a statistics kernel writes: straight into the caller's device array, else into a temporary that
+// finish() copies to the caller's host array (no caller array: discarded)
+struct StatusOut {
+    DevMem tmp;
+    int32_t *dev = nullptr;
+    int init(vp_batch *h, int32_t *status) {
+        dev = status && device_ptrs(h) ? status : nullptr;
+        if (dev) return 0;
+        if (int rc = tmp.alloc((size_t)h->B * sizeof(int32_t))) return rc;
+        dev = (int32_t *)tmp.p;
+        return 0;
+    }
+    int finish(vp_batch *h, int32_t *status) {
+        if (!status || device_ptrs(h)) return 0;
+        VP_HIP(hipMemcpyAsync(status, dev, (size_t)h->B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        VP_HIP(hipStreamSynchronize(h->stream));
+        return 0;
+    }
+};
+
+// ... and the handle's own four doubles into the caller's host array
+int read_sum4(vp_batch *h, double out[4]) {
+    VP_HIP(hipMemcpyAsync(out, h->d_sum4, 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    VP_HIP(hipStreamSynchronize(h->stream));
+    return VP_ERR_OK;
+}
+
+bool has_mrhs_set(const KernelEntry *k) { return k->mrhs_factor && k->mrhs_stream && k->mrhs_lm && k->mrhs_finish; }
 
 // run the evaluate kernel at h->d_alpha; any output may be null
 int run_evaluate(vp_batch *h, void *r_dev, void *J_dev, void *C_dev) {
@@ -546,24 +749,239 @@ struct DeviceGuard {
     DeviceGuard dev_guard__;                                                                                          \
     if (int rc__ = dev_guard__.enter((h)->device)) return rc__
 
-// == LevMarSolver::fit for problems with multiple right-hand sides (global fit): host-stepped loop of
-// {factor, streaming reduction over Y, LM step} launches; all LM state stays on the device, the host only
-// reads back one int (number of still-active problems) per iteration.
+// ---- global fit (S > 1): == LevMarSolver::fit for problems with multiple right-hand sides -------------------------------
+// Two kernel families.  The generic fallback runs the whole fit in one launch (mrhs_fit_generic).  The specialised
+// {factor, streaming reduction over Y, LM step} set is enqueued iteration by iteration, normally as a captured graph
+// (mrhs_fit_specialised); all LM state stays on the device, the host only looks at the number of still-active problems.
+struct MrhsFit {
+    vp_batch *h;
+    vp_lm_opts o;
+    LaunchParams p; // launches on the handle's stream; a capture works on a copy with its own stream
+    // right-hand sides sharded over ranks: the reduced sums of this rank's columns are totalled in a fixed order, summed
+    // over the ranks by the caller's collective (RCCL all-reduce of B*nacc doubles per evaluation) and fed to the LM step
+    // as a single slot; every rank then takes bit-identical decisions
+    int nacc = 0;
+    MrhsWs ws_tot = {};
+};
+
+// generic fallback kernels: the whole global fit is one launch (vp_generic.hpp, gen_mrhs_fit_kernel), which also leaves
+// the coefficients / cost / status of every column at the final point
+int mrhs_fit_generic(MrhsFit &f) {
+    vp_batch *h = f.h;
+    LaunchParams &p = f.p;
+    p.alpha_out = h->d_alpha;
+    p.C_out = h->d_C;
+    p.cost_out = h->d_cost_bs;
+    p.status = h->d_status_bs;
+    p.report = h->d_report;
+    // right-hand sides sharded over ranks: the same kernel in phases -- init, then per evaluation {sums of this rank's
+    // columns, the caller's all-reduce of B*(2 + q*q + q) doubles, LM step on the totals (every rank takes bit-identical
+    // decisions)}, then the per-column results at the final point
+    const int nacc = 2 + h->q * h->q + h->q;
+    if (h->rhs_allreduce) {
+        if (int rc = h->ensure(h->d_gen_lm, (size_t)h->B * h->kern->mrhs_state_bytes)) return rc;
+        if (int rc = h->ensure(h->d_mrhs_tot, (size_t)h->B * nacc * sizeof(double))) return rc;
+        if (int rc = h->ensure(h->d_gen_nactive, sizeof(int32_t))) return rc;
+        VP_HIP(hipMemsetAsync(h->d_gen_nactive, 0, sizeof(int32_t), h->stream));
+        p.gen_lm_state = h->d_gen_lm;
+        p.gen_acc = h->d_mrhs_tot;
+        p.gen_nactive = h->d_gen_nactive;
+        p.mrhs_S_global = h->rhs_global;
+    }
+    Timer tm(h, VP_KERNEL_FIT);
+    if (!h->rhs_allreduce) {
+        if (int rc = h->kern->mrhs_fit_whole(p)) return fail(rc, "generic global-fit launch failed");
+    } else {
+        p.gen_phase = 1;
+        if (int rc = h->kern->mrhs_fit_whole(p)) return fail(rc, "generic global-fit (init) launch failed");
+        const int max_iter = f.o.patience * (h->q + 1) + 2;
+        for (int it = 0; it < max_iter; ++it) {
+            p.gen_phase = 2;
+            if (int rc = h->kern->mrhs_fit_whole(p)) return fail(rc, "generic global-fit (sums) launch failed");
+            if (h->rhs_allreduce(h->d_mrhs_tot, h->B * nacc, (void *)h->stream, h->rhs_allreduce_user) != 0)
+                return fail(VP_ERR_INVALID, "the right-hand-side all-reduce callback reported an error");
+            p.gen_phase = 3;
+            if (int rc = h->kern->mrhs_fit_whole(p)) return fail(rc, "generic global-fit (step) launch failed");
+            if ((it & 3) == 3 || it + 1 == max_iter) {
+                int32_t nact = 0;
+                VP_HIP(hipMemcpyAsync(&nact, h->d_gen_nactive, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+                VP_HIP(hipStreamSynchronize(h->stream));
+                if (nact <= 0) break;
+            }
+        }
+        p.gen_phase = 4;
+        if (int rc = h->kern->mrhs_fit_whole(p)) return fail(rc, "generic global-fit (results) launch failed");
+    }
+    tm.stop();
+    return reduce_rhs(h);
+}
+
+// the first launch: LM state from alpha0 (the active count is SET there, no memset) + factorisation of alpha0
+int mrhs_enqueue_init(MrhsFit &f, LaunchParams &lp) {
+    lp.mrhs_init = 1;
+    lp.alpha = f.h->d_alpha;
+    lp.mrhs_io = f.h->h_io_dev;
+    const int rc = f.h->kern->mrhs_lm(lp);
+    lp.mrhs_init = 0;
+    return rc ? fail(rc, "mrhs_step (init) launch failed") : 0;
+}
+// one LM iteration = TWO launches: the streaming pass at the trial point, then the LM step on its sums fused with the
+// factorisation of the next trial point (mrhs_step_kernel).  The loop is device-driven: iterations are ENQUEUED with
+// no host synchronisation in between -- a problem whose LM loop has terminated is skipped on the device
+// (MrhsWs::done), so an iteration enqueued past the end costs two empty launches (~10 us).
+int mrhs_enqueue_iteration(MrhsFit &f, LaunchParams &lp) {
+    vp_batch *h = f.h;
+    lp.alpha = h->mrhs.alpha_trial;
+    lp.mrhs_mode = 0;
+    if (int rc = h->kern->mrhs_stream(lp)) return fail(rc, "mrhs_stream launch failed");
+    if (h->rhs_allreduce) {
+        const int64_t total = h->B * f.nacc;
+        hipLaunchKernelGGL(mrhs_reduce_partials_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                           lp.stream, (const double *)h->mrhs.acc, mrhs_gx(h->S, h->kern->mrhs_gx_cap > 0 ? h->kern->mrhs_gx_cap : 256), f.nacc, h->B,
+                           h->d_mrhs_tot);
+        VP_HIP(hipGetLastError());
+        if (h->rhs_allreduce(h->d_mrhs_tot, total, (void *)lp.stream, h->rhs_allreduce_user) != 0)
+            return fail(VP_ERR_INVALID, "the right-hand-side all-reduce callback reported an error");
+        lp.mrhs_ws = &f.ws_tot;
+        lp.mrhs_fws = &h->mrhs;
+        lp.mrhs_gx = 1;
+    }
+    // the LM step on the sums of this pass + the factorisation of the next trial point (one launch)
+    if (int rc = h->kern->mrhs_lm(lp)) return fail(rc, "mrhs_step launch failed");
+    lp.mrhs_ws = &h->mrhs;
+    lp.mrhs_fws = nullptr;
+    lp.mrhs_gx = 0;
+    return 0;
+}
+// final parameters + reports; coefficients, cost and status of every column at the final point come from the best
+// point's pass (double-buffered per-column results, MrhsWs::cbuf) -- no further pass over Y.  The m x S residual
+// matrix is produced on demand by vp_residuals, as after a single-RHS fit.  The finish kernel also leaves the active
+// count in pinned host memory (no copy kernel for the host's look at it).
+int mrhs_enqueue_finish(MrhsFit &f, LaunchParams &lp) {
+    vp_batch *h = f.h;
+    lp.alpha_out = h->d_alpha;
+    lp.report = h->d_report;
+    lp.C_out = h->d_C;
+    lp.cost_out = h->d_cost_bs;
+    lp.status = h->d_status_bs;
+    lp.mrhs_hflag = h->h_nactive_dev;
+    lp.mrhs_io = h->h_io_dev;
+    if (int rc = h->kern->mrhs_finish(lp)) return fail(rc, "mrhs_finish launch failed");
+    return reduce_rhs(h, lp.stream, true); // per-problem cost / status from the per-column ones
+}
+
+// [init,] `iters` iterations, finish as ONE instantiated graph.  Captured on the handle's private stream and replayed on
+// the handle's own
+bool mrhs_capture(MrhsFit &f, hipGraphExec_t &exec, const bool head, const int iters) {
+    MrhsGraphs &gr = f.h->graphs;
+    bool ok = true;
+    if (!gr.cap_stream) ok = hipStreamCreateWithFlags(&gr.cap_stream, hipStreamNonBlocking) == hipSuccess;
+    hipGraph_t g = nullptr;
+    if (ok) ok = hipStreamBeginCapture(gr.cap_stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    if (ok) {
+        LaunchParams gp = f.p;
+        gp.stream = gr.cap_stream;
+        if (head) ok = mrhs_enqueue_init(f, gp) == 0;
+        for (int it = 0; it < iters && ok; ++it) ok = mrhs_enqueue_iteration(f, gp) == 0;
+        if (ok) ok = mrhs_enqueue_finish(f, gp) == 0;
+        const bool ended = hipStreamEndCapture(gr.cap_stream, &g) == hipSuccess;
+        ok = ok && ended && g != nullptr;
+    }
+    if (ok) ok = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0) == hipSuccess;
+    if (g) (void)hipGraphDestroy(g);
+    if (!ok) {
+        (void)hipGetLastError();
+        exec = nullptr;
+    }
+    return ok;
+}
+// bring the handle's graphs up to date with this fit's options and the length its predecessor asks for (MrhsGraphs: the
+// policy); a failed capture leaves none, and plain launches for the rest of the handle's life
+void mrhs_update_graphs(MrhsFit &f) {
+    MrhsGraphs &gr = f.h->graphs;
+    if (!gr.head_stale(f.o)) return;
+    const bool opts_changed = gr.opts_changed(f.o);
+    const int want = gr.wanted_len();
+    if (gr.head) (void)hipGraphExecDestroy(gr.head);
+    gr.head = nullptr;
+    bool ok = mrhs_capture(f, gr.head, true, want);
+    if (ok && (opts_changed || !gr.tail)) {
+        if (gr.tail) (void)hipGraphExecDestroy(gr.tail);
+        gr.tail = nullptr;
+        ok = mrhs_capture(f, gr.tail, false, MrhsGraphs::kTailIters);
+    }
+    if (ok) {
+        gr.opts = f.o;
+        gr.len = want;
+    } else {
+        gr.drop();
+        gr.failed = true;
+    }
+}
+
+// The specialised kernel set.  The WHOLE fit as ONE captured HIP graph: init, `len` iterations, finish (no trace, no
+// all-reduce callback: both put host state into the launch sequence).  Its length follows the handle's previous fit:
+// repeated fits of similar data -- the streaming use this path is built for -- enqueue almost no idle iterations, and a
+// fit that needs more continues with further replays of the iteration-only tail graph.
+int mrhs_fit_specialised(MrhsFit &f) {
+    vp_batch *h = f.h;
+    LaunchParams &p = f.p;
+    MrhsGraphs &gr = h->graphs;
+    Timer tm(h, VP_KERNEL_FIT);
+    const int max_iter = f.o.patience * (h->q + 1) + 2;
+    f.nacc = 1 + h->n * h->n + h->p;
+    f.ws_tot = h->mrhs;
+    if (h->rhs_allreduce) {
+        if (int rc = h->ensure(h->d_mrhs_tot, (size_t)h->B * f.nacc * sizeof(double))) return rc;
+        f.ws_tot.acc = h->d_mrhs_tot;
+        p.mrhs_S_global = h->rhs_global;
+    }
+    const bool want_graph = !p.trace && !h->rhs_allreduce && !gr.failed;
+    if (want_graph) mrhs_update_graphs(f);
+    if (want_graph && gr.head) {
+        VP_HIP(hipGraphLaunch(gr.head, h->stream));
+        VP_HIP(hipStreamSynchronize(h->stream));
+        for (int it = gr.len; *(volatile int32_t *)h->h_nactive > 0 && it < max_iter; it += MrhsGraphs::kTailIters) {
+            VP_HIP(hipGraphLaunch(gr.tail, h->stream));
+            VP_HIP(hipStreamSynchronize(h->stream));
+        }
+        gr.observe(((volatile int32_t *)h->h_nactive)[1]);
+    } else {
+        if (int rc = mrhs_enqueue_init(f, p)) return rc;
+        int next_check = 12;
+        for (int it = 0; it < max_iter;) {
+            if (int rc = mrhs_enqueue_iteration(f, p)) return rc;
+            ++it;
+            if (it < next_check && it < max_iter) continue;
+            next_check += 24;
+            int32_t nact = 0;
+            VP_HIP(hipMemcpyAsync(&nact, h->mrhs.nactive, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            VP_HIP(hipStreamSynchronize(h->stream));
+            if (nact <= 0) break;
+        }
+        if (int rc = mrhs_enqueue_finish(f, p)) return rc;
+        // device-pointer handles: the finish / gather kernels read the caller's array addresses from the pinned MrhsIo record
+        // at EXECUTION time and nothing below waits for them on this path (no copies: they write the results themselves) --
+        // a following vp_fit would overwrite the record under them
+        if (device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream));
+    }
+    tm.stop();
+    return 0;
+}
+
 int mrhs_fit(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C_out, vp_report *rep, double *trace_out,
              int trace_rows) {
     if (!h->have_mrhs && !h->kern->mrhs_fit_whole) return fail(VP_ERR_UNSUPPORTED, "no MRHS kernels for this (model, m)");
-    vp_lm_opts o;
-    if (opts) o = *opts;
-    else vp_lm_opts_default(&o, h->dtype);
-    const size_t ts = tsize(h->dtype);
-    const hipMemcpyKind kin = device_ptrs(h) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    MrhsFit f;
+    f.h = h;
+    f.o = opts_or_default(h, opts);
     // device-pointer handles with the MRHS kernel set: the kernels read the initial parameters from, and write the results
     // into, the CALLER's arrays through a pinned record of their addresses (MrhsIo) -- no staging copies around the fit
     const bool use_io = device_ptrs(h) && h->have_mrhs;
     if (!h->h_nactive) {
-        VP_HIP(hipHostMalloc((void **)&h->h_nactive, 2 * sizeof(int32_t), hipHostMallocMapped));
+        if (int rc = h->alloc_pinned(h->h_nactive, 2 * sizeof(int32_t), hipHostMallocMapped)) return rc;
         VP_HIP(hipHostGetDevicePointer((void **)&h->h_nactive_dev, h->h_nactive, 0));
-        VP_HIP(hipHostMalloc((void **)&h->h_io, sizeof(MrhsIo), hipHostMallocMapped));
+        if (int rc = h->alloc_pinned(h->h_io, sizeof(MrhsIo), hipHostMallocMapped)) return rc;
         VP_HIP(hipHostGetDevicePointer((void **)&h->h_io_dev, h->h_io, 0));
         std::memset(h->h_io, 0, sizeof(MrhsIo));
     }
@@ -574,260 +992,69 @@ int mrhs_fit(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C_out
         h->h_io->rep_out = rep;
     } else {
         std::memset(h->h_io, 0, sizeof(MrhsIo));
-        VP_HIP(hipMemcpyAsync(h->d_alpha, alpha_inout, (size_t)h->B * h->q * ts, kin, h->stream));
+        if (int rc = upload_alpha(h, alpha_inout)) return rc;
     }
-    LaunchParams p;
-    fill_params(h, p);
-    p.mrhs_ws = &h->mrhs;
-    p.opts = &o;
+    fill_params(h, f.p);
+    f.p.mrhs_ws = &h->mrhs;
+    f.p.opts = &f.o;
     OutBuf tr;
-    const size_t tr_bytes = (size_t)h->B * (size_t)(trace_rows > 0 ? trace_rows : 0) * (h->q + 4) * sizeof(double);
-    if (trace_out && trace_rows > 0) {
-        if (int rc = tr.init(h, trace_out, tr_bytes)) return rc;
-        VP_HIP(hipMemsetAsync(tr.dptr, 0xFF, tr_bytes, h->stream));
-        p.trace = (double *)tr.dptr;
-        p.trace_rows = trace_rows;
+    if (int rc = trace_begin(h, tr, trace_out, trace_rows)) return rc;
+    set_trace(f.p, tr, trace_rows);
+    if (int rc = h->have_mrhs ? mrhs_fit_specialised(f) : mrhs_fit_generic(f)) return rc;
+    after_fit(h);
+    if (!use_io)
+        if (int rc = copy_fit_out(h, alpha_inout, C_out, rep)) return rc;
+    return tr.finish(h);
+}
+
+// pad the row dimension of `blocks` blocks from m to mp rows with `fill` (host arrays of 4- or 8-byte elements)
+void pad_rows_host(const void *src, void *dst, size_t blocks, int64_t m, int64_t mp, size_t ts, double fill) {
+    for (size_t blk = 0; blk < blocks; ++blk) {
+        std::memcpy((char *)dst + blk * mp * ts, (const char *)src + blk * m * ts, (size_t)m * ts);
+        for (int64_t i = m; i < mp; ++i) {
+            if (ts == 8) ((double *)dst)[blk * mp + i] = fill;
+            else ((float *)dst)[blk * mp + i] = (float)fill;
+        }
     }
-    if (!h->have_mrhs) {
-        // generic fallback kernels: the whole global fit is one launch (vp_generic.hpp, gen_mrhs_fit_kernel), which also
-        // leaves the coefficients / cost / status of every column at the final point
-        p.alpha_out = h->d_alpha;
-        p.C_out = h->d_C;
-        p.cost_out = h->d_cost_bs;
-        p.status = h->d_status_bs;
-        p.report = h->d_report;
-        if (h->rhs_allreduce) {
-            // right-hand sides sharded over ranks: the same kernel in phases -- init, then per evaluation {sums of this
-            // rank's columns, the caller's all-reduce of B*(2 + q*q + q) doubles, LM step on the totals (every rank takes
-            // bit-identical decisions)}, then the per-column results at the final point
-            const int nacc = 2 + h->q * h->q + h->q;
-            if (!h->d_gen_lm) VP_HIP(hipMalloc(&h->d_gen_lm, (size_t)h->B * h->kern->mrhs_state_bytes));
-            if (!h->d_mrhs_tot) VP_HIP(hipMalloc((void **)&h->d_mrhs_tot, (size_t)h->B * nacc * sizeof(double)));
-            if (!h->d_gen_nactive) VP_HIP(hipMalloc((void **)&h->d_gen_nactive, sizeof(int32_t)));
-            VP_HIP(hipMemsetAsync(h->d_gen_nactive, 0, sizeof(int32_t), h->stream));
-            p.gen_lm_state = h->d_gen_lm;
-            p.gen_acc = h->d_mrhs_tot;
-            p.gen_nactive = h->d_gen_nactive;
-            p.mrhs_S_global = h->rhs_global;
-            Timer tm(h, VP_KERNEL_FIT);
-            p.gen_phase = 1;
-            if (int rc = h->kern->mrhs_fit_whole(p)) return fail(rc, "generic global-fit (init) launch failed");
-            const int max_iter = o.patience * (h->q + 1) + 2;
-            for (int it = 0; it < max_iter; ++it) {
-                p.gen_phase = 2;
-                if (int rc = h->kern->mrhs_fit_whole(p)) return fail(rc, "generic global-fit (sums) launch failed");
-                if (h->rhs_allreduce(h->d_mrhs_tot, h->B * nacc, (void *)h->stream, h->rhs_allreduce_user) != 0)
-                    return fail(VP_ERR_INVALID, "the right-hand-side all-reduce callback reported an error");
-                p.gen_phase = 3;
-                if (int rc = h->kern->mrhs_fit_whole(p)) return fail(rc, "generic global-fit (step) launch failed");
-                if ((it & 3) == 3 || it + 1 == max_iter) {
-                    int32_t nact = 0;
-                    VP_HIP(hipMemcpyAsync(&nact, h->d_gen_nactive, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-                    VP_HIP(hipStreamSynchronize(h->stream));
-                    if (nact <= 0) break;
-                }
+}
+
+// ---- m < n: the caller's arrays as host arrays of mp rows per block (tiny problems by construction: padded on the host).
+// Grid: the last sample repeated; data: zeros; weights: zeros -- with unit weights on the caller's rows when it passed
+// none and `unit_w` asks for them.  An absent array (t of a caller-evaluated model; t and w of vp_set_observations) is
+// skipped.  Device arrays are read on `st`, with one synchronisation after the last of them.
+struct PaddedInputs {
+    std::vector<char> t, y, w;
+};
+int pad_inputs_host(PaddedInputs &out, bool on_device, hipStream_t st, size_t ts, int64_t m, int64_t mp, const void *t,
+                    size_t t_blocks, const void *Y, size_t y_blocks, const void *w, size_t w_blocks, bool unit_w) {
+    std::vector<char> th(t ? t_blocks * m * ts : 0), yh(y_blocks * m * ts), wh(w || unit_w ? w_blocks * m * ts : 0);
+    const void *src[3] = {t, Y, w};
+    std::vector<char> *host[3] = {&th, &yh, &wh};
+    for (int k = 0; k < 3; ++k) {
+        if (!src[k]) continue;
+        if (on_device) VP_HIP(hipMemcpyAsync(host[k]->data(), src[k], host[k]->size(), hipMemcpyDeviceToHost, st));
+        else std::memcpy(host[k]->data(), src[k], host[k]->size());
+    }
+    if (on_device) VP_HIP(hipStreamSynchronize(st));
+    if (t) {
+        out.t = std::vector<char>(t_blocks * mp * ts);
+        for (size_t blk = 0; blk < t_blocks; ++blk) {
+            const double last = ts == 8 ? ((const double *)th.data())[blk * m + m - 1] : (double)((const float *)th.data())[blk * m + m - 1];
+            pad_rows_host(th.data() + blk * m * ts, out.t.data() + blk * mp * ts, 1, m, mp, ts, last);
+        }
+    }
+    out.y = std::vector<char>(y_blocks * mp * ts);
+    pad_rows_host(yh.data(), out.y.data(), y_blocks, m, mp, ts, 0.0);
+    if (!wh.empty()) {
+        if (!w)
+            for (size_t i = 0; i < w_blocks * (size_t)m; ++i) {
+                if (ts == 8) ((double *)wh.data())[i] = 1.0;
+                else ((float *)wh.data())[i] = 1.0f;
             }
-            p.gen_phase = 4;
-            if (int rc = h->kern->mrhs_fit_whole(p)) return fail(rc, "generic global-fit (results) launch failed");
-            tm.stop();
-        } else {
-            Timer tm(h, VP_KERNEL_FIT);
-            if (int rc = h->kern->mrhs_fit_whole(p)) return fail(rc, "generic global-fit launch failed");
-            tm.stop();
-        }
-        if (int rc = reduce_rhs(h)) return rc;
-        h->have_params = true;
-        h->r_valid = false;
-        h->have_report = true;
-        if (int rc = copy_out(h, alpha_inout, h->d_alpha, (size_t)h->B * h->q * ts)) return rc;
-        if (int rc = copy_out(h, C_out, h->d_C, (size_t)h->B * h->S * h->n * ts)) return rc;
-        if (int rc = copy_out(h, rep, h->d_report, (size_t)h->B * sizeof(vp_report))) return rc;
-        if (int rc = tr.finish(h)) return rc;
-        return VP_ERR_OK;
+        out.w = std::vector<char>(w_blocks * mp * ts);
+        pad_rows_host(wh.data(), out.w.data(), w_blocks, m, mp, ts, 0.0);
     }
-    Timer tm(h, VP_KERNEL_FIT);
-    const int max_iter = o.patience * (h->q + 1) + 2;
-    // right-hand sides sharded over ranks: the reduced sums of this rank's columns are totalled in a fixed order,
-    // summed over the ranks by the caller's collective (RCCL all-reduce of B*(1+n*n+p) doubles per evaluation) and
-    // fed to the LM step as a single slot; every rank then takes bit-identical decisions.
-    const int nacc = 1 + h->n * h->n + h->p;
-    MrhsWs ws_tot = h->mrhs;
-    if (h->rhs_allreduce) {
-        if (!h->d_mrhs_tot) VP_HIP(hipMalloc((void **)&h->d_mrhs_tot, (size_t)h->B * nacc * sizeof(double)));
-        ws_tot.acc = h->d_mrhs_tot;
-        p.mrhs_S_global = h->rhs_global;
-    }
-    // the first launch: LM state from alpha0 (the active count is SET there, no memset) + factorisation of alpha0
-    auto enqueue_init = [&](LaunchParams &lp) -> int {
-        lp.mrhs_init = 1;
-        lp.alpha = h->d_alpha;
-        lp.mrhs_io = h->h_io_dev;
-        const int rc = h->kern->mrhs_lm(lp);
-        lp.mrhs_init = 0;
-        return rc ? fail(rc, "mrhs_step (init) launch failed") : 0;
-    };
-    // one LM iteration = TWO launches: the streaming pass at the trial point, then the LM step on its sums fused with the
-    // factorisation of the next trial point (mrhs_step_kernel).  The loop is device-driven: iterations are ENQUEUED with
-    // no host synchronisation in between -- a problem whose LM loop has terminated is skipped on the device
-    // (MrhsWs::done), so an iteration enqueued past the end costs two empty launches (~10 us).
-    auto enqueue_iteration = [&](LaunchParams &lp) -> int {
-        lp.alpha = h->mrhs.alpha_trial;
-        lp.mrhs_mode = 0;
-        if (int rc = h->kern->mrhs_stream(lp)) return fail(rc, "mrhs_stream launch failed");
-        if (h->rhs_allreduce) {
-            const int64_t total = h->B * nacc;
-            hipLaunchKernelGGL(mrhs_reduce_partials_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                               lp.stream, (const double *)h->mrhs.acc, mrhs_gx(h->S, h->kern->mrhs_gx_cap > 0 ? h->kern->mrhs_gx_cap : 256), nacc, h->B,
-                               h->d_mrhs_tot);
-            VP_HIP(hipGetLastError());
-            if (h->rhs_allreduce(h->d_mrhs_tot, total, (void *)lp.stream, h->rhs_allreduce_user) != 0)
-                return fail(VP_ERR_INVALID, "the right-hand-side all-reduce callback reported an error");
-            lp.mrhs_ws = &ws_tot;
-            lp.mrhs_fws = &h->mrhs;
-            lp.mrhs_gx = 1;
-        }
-        // the LM step on the sums of this pass + the factorisation of the next trial point (one launch)
-        if (int rc = h->kern->mrhs_lm(lp)) return fail(rc, "mrhs_step launch failed");
-        lp.mrhs_ws = &h->mrhs;
-        lp.mrhs_fws = nullptr;
-        lp.mrhs_gx = 0;
-        return 0;
-    };
-    // final parameters + reports; coefficients, cost and status of every column at the final point come from the best
-    // point's pass (double-buffered per-column results, MrhsWs::cbuf) -- no further pass over Y.  The m x S residual
-    // matrix is produced on demand by vp_residuals, as after a single-RHS fit.  The finish kernel also leaves the active
-    // count in pinned host memory (no copy kernel for the host's look at it).
-    auto enqueue_finish = [&](LaunchParams &lp) -> int {
-        lp.alpha_out = h->d_alpha;
-        lp.report = h->d_report;
-        lp.C_out = h->d_C;
-        lp.cost_out = h->d_cost_bs;
-        lp.status = h->d_status_bs;
-        lp.mrhs_hflag = h->h_nactive_dev;
-        lp.mrhs_io = h->h_io_dev;
-        if (int rc = h->kern->mrhs_finish(lp)) return fail(rc, "mrhs_finish launch failed");
-        return reduce_rhs(h, lp.stream, true); // per-problem cost / status from the per-column ones
-    };
-    // The WHOLE fit as ONE captured HIP graph: init, `iters` iterations, finish (no trace, no all-reduce callback: both
-    // put host state into the launch sequence).  Captured on a private stream -- the handle's stream may be the null
-    // stream, which cannot be captured -- and replayed on the handle's stream.  The graph holds the LM options by
-    // value: it is re-captured when they change.  Its length follows the handle's previous fit (evaluations + 1 spare
-    // iteration, at least 6; 12 for the first fit): repeated fits of similar data -- the streaming use this path is
-    // built for -- enqueue almost no idle iterations, and a fit that needs more continues with further replays of the
-    // iteration-only tail graph.
-    const bool want_graph = !p.trace && !h->rhs_allreduce && !h->mrhs_graph_failed;
-    int want_iters = h->mrhs_graph_iters > 0 ? h->mrhs_graph_iters : 12;
-    auto capture = [&](hipGraphExec_t &exec, const bool head, const int iters) -> bool {
-        bool ok = true;
-        if (!h->cap_stream) ok = hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking) == hipSuccess;
-        hipGraph_t g = nullptr;
-        if (ok) ok = hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-        if (ok) {
-            LaunchParams gp = p;
-            gp.stream = h->cap_stream;
-            if (head) ok = enqueue_init(gp) == 0;
-            for (int it = 0; it < iters && ok; ++it) ok = enqueue_iteration(gp) == 0;
-            if (ok) ok = enqueue_finish(gp) == 0;
-            const bool ended = hipStreamEndCapture(h->cap_stream, &g) == hipSuccess;
-            ok = ok && ended && g != nullptr;
-        }
-        if (ok) ok = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0) == hipSuccess;
-        if (g) (void)hipGraphDestroy(g);
-        if (!ok) {
-            (void)hipGetLastError();
-            exec = nullptr;
-        }
-        return ok;
-    };
-    // Re-capture with hysteresis: on streaming data the longest fit moves by +-1 evaluation from one call to the next, and a
-    // capture + instantiation costs as much as the fit it speeds up.  The head is re-captured when the options changed, when
-    // the wanted length EXCEEDS the captured one (every further iteration would cost a replay of the tail graph) or falls
-    // short of it by 4 or more (each idle iteration is two empty launches, ~10 us); the 12-iteration tail graph does not
-    // depend on the length and is only re-captured with the options.
-    const bool opts_changed = !h->mrhs_graph || std::memcmp(&h->mrhs_graph_opts, &o, sizeof(o)) != 0;
-    // (a handle whose last VP_MRHS_EXACT_AFTER + 1 fits took the same number of evaluations drops the spare iteration -- two
-    // empty launches, ~10 us of a 0.7 ms fit: want_iters is then exact and the head is re-captured ONCE, down to that length.
-    // The exact length only ever SHRINKS the graph: a stream whose longest fit moves by +-1 every few calls (A A A B A A A B)
-    // never reaches the run length, and after a miss the spare-iteration rule above decides alone -- no recapture per
-    // fluctuation.)
-    const bool exact = h->mrhs_same_count >= VP_MRHS_EXACT_AFTER;
-    if (want_graph && (opts_changed || want_iters > h->mrhs_graph_len || want_iters + 4 <= h->mrhs_graph_len ||
-                       (exact && want_iters < h->mrhs_graph_len))) {
-        if (h->mrhs_graph) (void)hipGraphExecDestroy(h->mrhs_graph);
-        h->mrhs_graph = nullptr;
-        bool ok = capture(h->mrhs_graph, true, want_iters);
-        if (ok && (opts_changed || !h->mrhs_graph_tail)) {
-            if (h->mrhs_graph_tail) (void)hipGraphExecDestroy(h->mrhs_graph_tail);
-            h->mrhs_graph_tail = nullptr;
-            ok = capture(h->mrhs_graph_tail, false, 12);
-        }
-        if (ok) {
-            h->mrhs_graph_opts = o;
-            h->mrhs_graph_len = want_iters;
-        } else {
-            if (h->mrhs_graph) (void)hipGraphExecDestroy(h->mrhs_graph);
-            if (h->mrhs_graph_tail) (void)hipGraphExecDestroy(h->mrhs_graph_tail);
-            h->mrhs_graph = h->mrhs_graph_tail = nullptr;
-            h->mrhs_graph_failed = true; // fall back to plain launches for the rest of this handle's life
-        }
-    }
-    // device-pointer handles: the copies into the caller's arrays are enqueued right behind the graph, BEFORE the host
-    // waits for the active count (a fit that outlasts the graph repeats them after the tail graph)
-    bool outputs_done = use_io; // (written by the finish / gather kernels themselves)
-    auto early_outputs = [&]() -> int {
-        if (outputs_done || !device_ptrs(h) || tr.tmp) return 0;
-        if (int rc = copy_out(h, alpha_inout, h->d_alpha, (size_t)h->B * h->q * ts)) return rc;
-        if (int rc = copy_out(h, C_out, h->d_C, (size_t)h->B * h->S * h->n * ts)) return rc;
-        if (int rc = copy_out(h, rep, h->d_report, (size_t)h->B * sizeof(vp_report))) return rc;
-        outputs_done = true;
-        return 0;
-    };
-    if (want_graph && h->mrhs_graph) {
-        VP_HIP(hipGraphLaunch(h->mrhs_graph, h->stream));
-        if (int rc = early_outputs()) return rc;
-        VP_HIP(hipStreamSynchronize(h->stream));
-        for (int it = h->mrhs_graph_len; *(volatile int32_t *)h->h_nactive > 0 && it < max_iter; it += 12) {
-            VP_HIP(hipGraphLaunch(h->mrhs_graph_tail, h->stream));
-            if (int rc = early_outputs()) return rc;
-            VP_HIP(hipStreamSynchronize(h->stream));
-        }
-        // the next capture: as many iterations as this fit's longest problem took evaluations, plus one spare
-        const int nfev_max = ((volatile int32_t *)h->h_nactive)[1];
-        h->mrhs_same_count = (nfev_max == h->mrhs_prev_nfev) ? h->mrhs_same_count + 1 : 0;
-        h->mrhs_prev_nfev = nfev_max;
-        int it_next = nfev_max + (h->mrhs_same_count >= VP_MRHS_EXACT_AFTER ? 0 : 1);
-        it_next = it_next < 6 ? 6 : (it_next > 24 ? 24 : it_next);
-        h->mrhs_graph_iters = it_next;
-    } else {
-        if (int rc = enqueue_init(p)) return rc;
-        int next_check = 12;
-        for (int it = 0; it < max_iter;) {
-            if (int rc = enqueue_iteration(p)) return rc;
-            ++it;
-            if (it < next_check && it < max_iter) continue;
-            next_check += 24;
-            int32_t nact = 0;
-            VP_HIP(hipMemcpyAsync(&nact, h->mrhs.nactive, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            VP_HIP(hipStreamSynchronize(h->stream));
-            if (nact <= 0) break;
-        }
-        if (int rc = enqueue_finish(p)) return rc;
-        // device-pointer handles: the finish / gather kernels read the caller's array addresses from the pinned MrhsIo record
-        // at EXECUTION time and nothing below waits for them on this path (no copies: they write the results themselves) --
-        // a following vp_fit would overwrite the record under them
-        if (use_io) VP_HIP(hipStreamSynchronize(h->stream));
-    }
-    tm.stop();
-    h->have_params = true;
-    h->r_valid = false;
-    h->have_report = true;
-    if (!outputs_done) {
-        if (int rc = copy_out(h, alpha_inout, h->d_alpha, (size_t)h->B * h->q * ts)) return rc;
-        if (int rc = copy_out(h, C_out, h->d_C, (size_t)h->B * h->S * h->n * ts)) return rc;
-        if (int rc = copy_out(h, rep, h->d_report, (size_t)h->B * sizeof(vp_report))) return rc;
-    }
-    if (int rc = tr.finish(h)) return rc;
-    return VP_ERR_OK;
+    return 0;
 }
 
 } // namespace
@@ -865,68 +1092,42 @@ struct ExtSpec {
 };
 static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dtype, int64_t m, int64_t S, int64_t B,
                              const void *t, const void *Y, const void *w, double svd_epsilon, int flags, int device,
-                             void *hip_stream, bool data_on_device, const ExtSpec *ext = nullptr);
+                             void *hip_stream, bool data_on_device, const ExtSpec *ext);
 
-// pad the row dimension of `blocks` blocks from m to mp rows with `fill` (host arrays of 4- or 8-byte elements)
-static void pad_rows_host(const void *src, void *dst, size_t blocks, int64_t m, int64_t mp, size_t ts, double fill) {
-    for (size_t blk = 0; blk < blocks; ++blk) {
-        std::memcpy((char *)dst + blk * mp * ts, (const char *)src + blk * m * ts, (size_t)m * ts);
-        for (int64_t i = m; i < mp; ++i) {
-            if (ts == 8) ((double *)dst)[blk * mp + i] = fill;
-            else ((float *)dst)[blk * mp + i] = (float)fill;
-        }
+// both create entry points.  m < n: the reference solves the underdetermined linear sub-problem by its truncated SVD
+// (minimum-norm coefficients, src/solvers/levmar/mod.rs:51-54).  Here: n - m extra rows of ZERO weight (grid value = the
+// last sample, data 0) -- they change neither the minimum-norm solution, nor the residual, nor a non-zero singular value --
+// and the handle strips them from every array that crosses the ABI (m_user).  A caller-evaluated model's Phi / dPhi keep
+// THEIR m rows (LaunchParams::ext_rows), the kernels read the missing rows as zeros.
+static int batch_create(vp_batch **out, const vp_model_desc *model, int dtype, int64_t m, int64_t S, int64_t B, const void *t,
+                        const void *Y, const void *w, double svd_epsilon, int flags, int device, void *hip_stream,
+                        const ExtSpec *ext) {
+    const bool dev_data = (flags & VP_FLAG_DEVICE_PTRS) != 0;
+    // (arguments batch_create_impl refuses go to it as they are, for its message)
+    if (!out || !model || !Y || (!t && !ext) || m <= 0 || S <= 0 || B <= 0 || (dtype != VP_F64 && dtype != VP_F32) ||
+        m >= model->n_basis || model->n_basis > VP_MAX_BASIS)
+        return batch_create_impl(out, model, dtype, m, S, B, t, Y, w, svd_epsilon, flags, device, hip_stream, dev_data, ext);
+    PaddedInputs pad;
+    DeviceGuard guard;
+    hipStream_t st = nullptr;
+    if (dev_data) {
+        if (vp_device_count() <= 0) return fail(VP_ERR_NO_DEVICE, "no HIP device visible");
+        if (int rc = guard.enter(device)) return rc;
+        st = (flags & VP_FLAG_OWN_STREAM) ? nullptr : (hipStream_t)hip_stream;
     }
+    const size_t tb = (flags & VP_FLAG_T_PER_PROBLEM) ? (size_t)B : 1, wb = (flags & VP_FLAG_W_PER_PROBLEM) ? (size_t)B : 1;
+    if (int rc = pad_inputs_host(pad, dev_data, st, tsize(dtype), m, model->n_basis, t, tb, Y, (size_t)B * S, w, wb, true))
+        return rc;
+    const int rc = batch_create_impl(out, model, dtype, model->n_basis, S, B, t ? pad.t.data() : nullptr, pad.y.data(),
+                                     pad.w.data(), svd_epsilon, flags, device, hip_stream, false, ext);
+    if (rc == VP_ERR_OK) (*out)->m_user = m;
+    return rc;
 }
 
 int vp_batch_create(vp_batch **out, const vp_model_desc *model, int dtype, int64_t m, int64_t S, int64_t B,
                     const void *t, const void *Y, const void *w, double svd_epsilon, int flags, int device,
                     void *hip_stream) {
-    const bool dev_data = (flags & VP_FLAG_DEVICE_PTRS) != 0;
-    if (!out || !model || !Y || !t || m <= 0 || S <= 0 || B <= 0 || (dtype != VP_F64 && dtype != VP_F32) || m >= model->n_basis ||
-        model->n_basis > VP_MAX_BASIS)
-        return batch_create_impl(out, model, dtype, m, S, B, t, Y, w, svd_epsilon, flags, device, hip_stream, dev_data);
-    // m < n: the reference solves the underdetermined linear sub-problem by its truncated SVD (minimum-norm coefficients,
-    // src/solvers/levmar/mod.rs:51-54).  Here: n - m extra rows of ZERO weight (grid value = the last sample, data 0) --
-    // they change neither the minimum-norm solution, nor the residual, nor a non-zero singular value -- and the handle
-    // strips them from every array that crosses the ABI (m_user).  Tiny problems by construction: padded on the host.
-    const size_t ts = dtype == VP_F64 ? 8 : 4;
-    const int64_t mp = model->n_basis;
-    const size_t tb = (flags & VP_FLAG_T_PER_PROBLEM) ? (size_t)B : 1, wb = (flags & VP_FLAG_W_PER_PROBLEM) ? (size_t)B : 1;
-    std::vector<char> th(tb * m * ts), yh((size_t)B * S * m * ts), wh(w ? wb * m * ts : 0);
-    if (dev_data) {
-        if (vp_device_count() <= 0) return fail(VP_ERR_NO_DEVICE, "no HIP device visible");
-        DeviceGuard g__;
-        if (int rc = g__.enter(device)) return rc;
-        hipStream_t st = (flags & VP_FLAG_OWN_STREAM) ? nullptr : (hipStream_t)hip_stream;
-        VP_HIP(hipMemcpyAsync(th.data(), t, th.size(), hipMemcpyDeviceToHost, st));
-        VP_HIP(hipMemcpyAsync(yh.data(), Y, yh.size(), hipMemcpyDeviceToHost, st));
-        if (w) VP_HIP(hipMemcpyAsync(wh.data(), w, wh.size(), hipMemcpyDeviceToHost, st));
-        VP_HIP(hipStreamSynchronize(st));
-    } else {
-        std::memcpy(th.data(), t, th.size());
-        std::memcpy(yh.data(), Y, yh.size());
-        if (w) std::memcpy(wh.data(), w, wh.size());
-    }
-    std::vector<char> tp(tb * mp * ts), yp((size_t)B * S * mp * ts), wp(wb * mp * ts);
-    for (size_t blk = 0; blk < tb; ++blk) { // grid: repeat the last sample
-        const double last = ts == 8 ? ((const double *)th.data())[blk * m + m - 1] : (double)((const float *)th.data())[blk * m + m - 1];
-        pad_rows_host(th.data() + blk * m * ts, tp.data() + blk * mp * ts, 1, m, mp, ts, last);
-    }
-    pad_rows_host(yh.data(), yp.data(), (size_t)B * S, m, mp, ts, 0.0);
-    if (w) {
-        pad_rows_host(wh.data(), wp.data(), wb, m, mp, ts, 0.0);
-    } else { // unit weights on the caller's rows, zero on the padding
-        std::vector<char> ones(wb * m * ts);
-        for (size_t i = 0; i < wb * (size_t)m; ++i) {
-            if (ts == 8) ((double *)ones.data())[i] = 1.0;
-            else ((float *)ones.data())[i] = 1.0f;
-        }
-        pad_rows_host(ones.data(), wp.data(), wb, m, mp, ts, 0.0);
-    }
-    const int rc = batch_create_impl(out, model, dtype, mp, S, B, tp.data(), yp.data(), wp.data(), svd_epsilon, flags, device, hip_stream,
-                                     false);
-    if (rc == VP_ERR_OK) (*out)->m_user = m;
-    return rc;
+    return batch_create(out, model, dtype, m, S, B, t, Y, w, svd_epsilon, flags, device, hip_stream, nullptr);
 }
 
 // == SeparableProblemBuilder::build (src/problem/builder.rs:278-324) for a model the caller evaluates: any
@@ -957,39 +1158,114 @@ int vp_batch_create_external(vp_batch **out, int32_t n_basis, int32_t n_params, 
         for (int a = 0; a < VP_MAX_BASIS_PARAMS; ++a) md.param[j][a] = -1;
     }
     const ExtSpec ext{n_pairs, pair_basis, pair_param};
-    const bool dev_data = (flags & VP_FLAG_DEVICE_PTRS) != 0;
-    if (!Y || m <= 0 || S <= 0 || B <= 0 || (dtype != VP_F64 && dtype != VP_F32) || m >= n_basis)
-        return batch_create_impl(out, &md, dtype, m, S, B, nullptr, Y, w, svd_epsilon, flags, device, hip_stream, dev_data, &ext);
-    // m < n: as vp_batch_create -- n - m extra rows of zero weight; the caller's Phi / dPhi keep THEIR m rows
-    // (LaunchParams::ext_rows), the kernels read the missing rows as zeros
-    const size_t ts = dtype == VP_F64 ? 8 : 4;
-    const int64_t mp = n_basis;
-    const size_t wb = (flags & VP_FLAG_W_PER_PROBLEM) ? (size_t)B : 1;
-    std::vector<char> yh((size_t)B * S * m * ts), wh(wb * m * ts);
-    if (dev_data) {
-        if (vp_device_count() <= 0) return fail(VP_ERR_NO_DEVICE, "no HIP device visible");
-        DeviceGuard g__;
-        if (int rc = g__.enter(device)) return rc;
-        hipStream_t st = (flags & VP_FLAG_OWN_STREAM) ? nullptr : (hipStream_t)hip_stream;
-        VP_HIP(hipMemcpyAsync(yh.data(), Y, yh.size(), hipMemcpyDeviceToHost, st));
-        if (w) VP_HIP(hipMemcpyAsync(wh.data(), w, wh.size(), hipMemcpyDeviceToHost, st));
-        VP_HIP(hipStreamSynchronize(st));
+    return batch_create(out, &md, dtype, m, S, B, nullptr, Y, w, svd_epsilon, flags, device, hip_stream, &ext);
+}
+
+// the handle's buffers, data and kernel-side state; on an error the caller destroys the handle
+static int batch_init(vp_batch *h, const void *t, const void *Y, const void *w, void *hip_stream, const bool data_on_device) {
+    const int flags = h->flags;
+    const int64_t m = h->m, S = h->S, B = h->B;
+    if (!(flags & VP_FLAG_OWN_STREAM)) {
+        h->stream = (hipStream_t)hip_stream; // NULL == the null stream (PyTorch's default stream)
     } else {
-        std::memcpy(yh.data(), Y, yh.size());
-        if (w) std::memcpy(wh.data(), w, wh.size());
+        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(VP_ERR_HIP, "hipStreamCreate failed");
+        h->own_stream = true;
     }
-    if (!w)
-        for (size_t i = 0; i < wb * (size_t)m; ++i) {
-            if (ts == 8) ((double *)wh.data())[i] = 1.0;
-            else ((float *)wh.data())[i] = 1.0f;
+    const size_t ts = tsize(h->dtype);
+    const size_t t_elems = (size_t)((flags & VP_FLAG_T_PER_PROBLEM) ? B * m : m);
+    const size_t w_elems = (size_t)((flags & VP_FLAG_W_PER_PROBLEM) ? B * m : m);
+    const size_t y_elems = (size_t)B * S * m;
+    const hipMemcpyKind kin = data_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (t) { // (a caller-evaluated model has no grid)
+        if (int rc = h->alloc(h->d_t, t_elems * ts)) return rc;
+        VP_HIP(hipMemcpyAsync(h->d_t, t, t_elems * ts, kin, h->stream));
+    }
+    if (w) {
+        if (int rc = h->alloc(h->d_w, w_elems * ts)) return rc;
+        VP_HIP(hipMemcpyAsync(h->d_w, w, w_elems * ts, kin, h->stream));
+    }
+    {
+        // the two temporaries of create: freed (the staged data first) once the stream has drained
+        DevMem gflag_mem, ytmp;
+        int *d_gflag = nullptr;
+        // (fp32 handles: only the Gram fit kernel, vp_fitg.hpp, uses the flag -- the other fp32 kernels have no recurrence)
+        const bool try_uniform = t && m >= 3 && !(flags & VP_FLAG_NO_GRID_RECURRENCE);
+        if (try_uniform) {
+            const int one = 1;
+            if (int rc = gflag_mem.alloc(sizeof(int))) return rc;
+            d_gflag = (int *)gflag_mem.p;
+            VP_HIP(hipMemcpyAsync(d_gflag, &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
+            const int64_t ngrids = (flags & VP_FLAG_T_PER_PROBLEM) ? B : 1;
+            if (h->dtype == VP_F64)
+                hipLaunchKernelGGL(grid_check_kernel<double>, dim3((unsigned)ngrids), dim3(256), 0, h->stream,
+                                   (const double *)h->d_t, (int)m, ngrids, d_gflag);
+            else
+                hipLaunchKernelGGL(grid_check_kernel<float>, dim3((unsigned)ngrids), dim3(256), 0, h->stream,
+                                   (const float *)h->d_t, (int)m, ngrids, d_gflag);
+            VP_HIP(hipGetLastError());
         }
-    std::vector<char> yp((size_t)B * S * mp * ts), wp(wb * mp * ts);
-    pad_rows_host(yh.data(), yp.data(), (size_t)B * S, m, mp, ts, 0.0);
-    pad_rows_host(wh.data(), wp.data(), wb, m, mp, ts, 0.0);
-    const int rc = batch_create_impl(out, &md, dtype, mp, S, B, nullptr, yp.data(), wp.data(), svd_epsilon, flags, device,
-                                     hip_stream, false, &ext);
-    if (rc == VP_ERR_OK) (*out)->m_user = m;
-    return rc;
+        if (int rc = h->alloc(h->d_yw, y_elems * ts)) return rc;
+        // Y_w = W * Y
+        const void *ysrc = Y;
+        if (!data_on_device) {
+            if (int rc = ytmp.alloc(y_elems * ts)) return rc;
+            VP_HIP(hipMemcpyAsync(ytmp.p, Y, y_elems * ts, hipMemcpyHostToDevice, h->stream));
+            ysrc = ytmp.p;
+        }
+        if (int rc = launch_weight_data(h, ysrc)) return rc;
+        int gflag = 0;
+        if (d_gflag) VP_HIP(hipMemcpyAsync(&gflag, d_gflag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        VP_HIP(hipStreamSynchronize(h->stream));
+        h->grid_uniform = gflag != 0;
+    }
+    if (int rc = h->alloc(h->d_alpha, (size_t)std::max<int64_t>(1, B * h->q) * ts)) return rc;
+    if (int rc = h->alloc(h->d_C, (size_t)B * S * h->n * ts)) return rc;
+    if (int rc = h->alloc(h->d_cost_bs, (size_t)B * S * sizeof(double))) return rc;
+    if (int rc = h->alloc(h->d_status_bs, (size_t)B * S * sizeof(int32_t))) return rc;
+    if (S == 1) { // one column per problem: the per-problem arrays ARE the per-column ones (reduce_rhs has nothing to do)
+        h->d_cost = h->d_cost_bs;
+        h->d_status = h->d_status_bs;
+    } else {
+        if (int rc = h->alloc(h->d_cost, (size_t)B * sizeof(double))) return rc;
+        if (int rc = h->alloc(h->d_status, (size_t)B * sizeof(int32_t))) return rc;
+    }
+    if (int rc = h->alloc(h->d_report, (size_t)B * sizeof(vp_report))) return rc;
+    if (int rc = h->alloc(h->d_sum4, 4 * sizeof(double))) return rc;
+    if (int rc = h->alloc(h->d_queue, sizeof(int))) return rc;
+    // (caller-evaluated models allocate the generic workspace on first use: their resident kernels -- vp_ext.hpp -- need none)
+    if (!h->external)
+        if (int rc = ensure_gen_ws(h)) return rc;
+    VP_HIP(hipEventCreate(&h->ev0));
+    VP_HIP(hipEventCreate(&h->ev1));
+    if (S > 1 && has_mrhs_set(h->kern)) {
+        const int n_ = h->n, p_ = h->p, q_ = h->q;
+        MrhsWs &ws = h->mrhs;
+        if (int rc = h->alloc(ws.qthin, (size_t)B * n_ * m * ts)) return rc;
+        if (int rc = h->alloc(ws.g, (size_t)B * std::max(1, p_) * m * ts)) return rc;
+        if (int rc = h->alloc(ws.small, (size_t)B * mrhs_small_stride_rt(n_, p_) * sizeof(double))) return rc;
+        if (int rc = h->alloc(ws.statusA, (size_t)B * sizeof(int32_t))) return rc;
+        // partial-sum slots of the MODE 0 pass (the only writer): gx is fixed per handle -- min(ceil(S/8), the kernel set's
+        // cap) -- not the upper bound VP_MRHS_GX_MAX (B = 70000, S = 2 needs 1 slot per problem, not 512)
+        const int gx_acc = mrhs_gx(S, h->kern->mrhs_gx_cap > 0 ? h->kern->mrhs_gx_cap : 256);
+        if (gx_acc > VP_MRHS_GX_MAX) return fail(VP_ERR_INVALID, "internal: partial-sum slots per problem exceed VP_MRHS_GX_MAX");
+        if (int rc = h->alloc(ws.acc, (size_t)B * gx_acc * (1 + n_ * n_ + p_) * sizeof(double))) return rc;
+        if (int rc = h->alloc(ws.lm_state, (size_t)B * h->kern->mrhs_state_bytes)) return rc;
+        if (int rc = h->alloc(ws.nactive, 2 * sizeof(int32_t))) return rc;
+        if (int rc = h->alloc(ws.done, (size_t)B * sizeof(int32_t))) return rc;
+        VP_HIP(hipMemsetAsync(ws.done, 0, (size_t)B * sizeof(int32_t), h->stream));
+        if (int rc = h->alloc(ws.alpha_trial, (size_t)std::max<int64_t>(1, B * q_) * ts)) return rc;
+        for (int i = 0; i < 2; ++i) {
+            if (int rc = h->alloc(ws.cbuf[i], (size_t)B * S * n_ * ts)) return rc;
+            if (int rc = h->alloc(ws.costbuf[i], (size_t)B * S * sizeof(double))) return rc;
+            if (int rc = h->alloc(ws.stbuf[i], (size_t)B * S * sizeof(int32_t))) return rc;
+        }
+        if (int rc = h->alloc(ws.widx, (size_t)B * sizeof(int32_t))) return rc;
+        if (int rc = h->alloc(ws.bidx, (size_t)B * sizeof(int32_t))) return rc;
+        if (int rc = h->alloc(ws.jcond, (size_t)B * sizeof(double))) return rc;
+        VP_HIP(hipMemsetAsync(ws.jcond, 0, (size_t)B * sizeof(double), h->stream));
+        h->have_mrhs = true;
+    }
+    return VP_ERR_OK;
 }
 
 static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dtype, int64_t m, int64_t S, int64_t B,
@@ -1032,11 +1308,9 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
     if (!kern) kern = generic_kernels(dtype);
     // a global fit (S > 1) on a specialised set WITHOUT multiple-right-hand-side kernels (the multi-wave sets: double
     // exponential at 2048 < m <= 4096, the fp32 Gram shape) runs on the generic kernels as well
-    if (!ext && S > 1 && !(kern->mrhs_factor && kern->mrhs_stream && kern->mrhs_lm && kern->mrhs_finish) && !kern->mrhs_fit_whole)
-        kern = generic_kernels(dtype);
+    if (!ext && S > 1 && !has_mrhs_set(kern) && !kern->mrhs_fit_whole) kern = generic_kernels(dtype);
 
     vp_batch *h = new vp_batch();
-    std::memset(h, 0, sizeof(*h));
     h->model = *model;
     h->dtype = dtype;
     h->m = m;
@@ -1059,139 +1333,10 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
             h->ext_pp[i] = ext->pp[i];
         }
     }
-    if (!(flags & VP_FLAG_OWN_STREAM)) {
-        h->stream = (hipStream_t)hip_stream; // NULL == the null stream (PyTorch's default stream)
-        h->own_stream = false;
-    } else {
-        hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            delete h;
-            return fail(VP_ERR_HIP, "hipStreamCreate failed");
-        }
-        h->own_stream = true;
+    if (int rc = batch_init(h, t, Y, w, hip_stream, data_on_device)) {
+        vp_batch_destroy(h);
+        return rc;
     }
-    const size_t ts = tsize(dtype);
-    const size_t t_elems = (size_t)((flags & VP_FLAG_T_PER_PROBLEM) ? B * m : m);
-    const size_t w_elems = (size_t)((flags & VP_FLAG_W_PER_PROBLEM) ? B * m : m);
-    const size_t y_elems = (size_t)B * S * m;
-#define VP_TRY(expr)                                                                                                  \
-    do {                                                                                                              \
-        hipError_t e__ = (expr);                                                                                      \
-        if (e__ != hipSuccess) {                                                                                      \
-            std::string msg__ = std::string(#expr) + ": " + hipGetErrorString(e__);                                 \
-            vp_batch_destroy(h);                                                                                      \
-            return fail(VP_ERR_HIP, msg__);                                                                           \
-        }                                                                                                             \
-    } while (0)
-    const hipMemcpyKind kin = data_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (t) { // (a caller-evaluated model has no grid)
-        VP_TRY(hipMalloc(&h->d_t, t_elems * ts));
-        VP_TRY(hipMemcpyAsync(h->d_t, t, t_elems * ts, kin, h->stream));
-    }
-    if (w) {
-        VP_TRY(hipMalloc(&h->d_w, w_elems * ts));
-        VP_TRY(hipMemcpyAsync(h->d_w, w, w_elems * ts, kin, h->stream));
-    }
-    int *&d_gflag = reinterpret_cast<int *&>(h->tmp_a);
-    // (fp32 handles: only the Gram fit kernel, vp_fitg.hpp, uses the flag -- the other fp32 kernels have no recurrence)
-    const bool try_uniform = t && m >= 3 && !(flags & VP_FLAG_NO_GRID_RECURRENCE);
-    if (try_uniform) {
-        const int one = 1;
-        VP_TRY(hipMalloc((void **)&d_gflag, sizeof(int)));
-        VP_TRY(hipMemcpyAsync(d_gflag, &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
-        const int64_t ngrids = (flags & VP_FLAG_T_PER_PROBLEM) ? B : 1;
-        if (dtype == VP_F64)
-            hipLaunchKernelGGL(grid_check_kernel<double>, dim3((unsigned)ngrids), dim3(256), 0, h->stream,
-                               (const double *)h->d_t, (int)m, ngrids, d_gflag);
-        else
-            hipLaunchKernelGGL(grid_check_kernel<float>, dim3((unsigned)ngrids), dim3(256), 0, h->stream,
-                               (const float *)h->d_t, (int)m, ngrids, d_gflag);
-        VP_TRY(hipGetLastError());
-    }
-    VP_TRY(hipMalloc(&h->d_yw, y_elems * ts));
-    {
-        // Y_w = W * Y
-        void *&ytmp = h->tmp_b;
-        const void *ysrc = Y;
-        if (!data_on_device) {
-            VP_TRY(hipMalloc(&ytmp, y_elems * ts));
-            VP_TRY(hipMemcpyAsync(ytmp, Y, y_elems * ts, hipMemcpyHostToDevice, h->stream));
-            ysrc = ytmp;
-        }
-        const int64_t total = (int64_t)y_elems;
-        const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 65536);
-        const int64_t wstride = (flags & VP_FLAG_W_PER_PROBLEM) ? m : 0;
-        if (dtype == VP_F64)
-            hipLaunchKernelGGL(weight_data_kernel<double>, dim3(grid), dim3(256), 0, h->stream, (const double *)ysrc,
-                               (const double *)h->d_w, (double *)h->d_yw, (int)m, S, wstride, total);
-        else
-            hipLaunchKernelGGL(weight_data_kernel<float>, dim3(grid), dim3(256), 0, h->stream, (const float *)ysrc,
-                               (const float *)h->d_w, (float *)h->d_yw, (int)m, S, wstride, total);
-        VP_TRY(hipGetLastError());
-        int gflag = 0;
-        if (d_gflag) VP_TRY(hipMemcpyAsync(&gflag, d_gflag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        VP_TRY(hipStreamSynchronize(h->stream));
-        (void)hipFree(ytmp);
-        ytmp = nullptr;
-        (void)hipFree(d_gflag);
-        d_gflag = nullptr;
-        h->grid_uniform = gflag != 0;
-    }
-    VP_TRY(hipMalloc(&h->d_alpha, (size_t)std::max<int64_t>(1, B * h->q) * ts));
-    VP_TRY(hipMalloc(&h->d_C, (size_t)B * S * h->n * ts));
-    VP_TRY(hipMalloc((void **)&h->d_cost_bs, (size_t)B * S * sizeof(double)));
-    VP_TRY(hipMalloc((void **)&h->d_status_bs, (size_t)B * S * sizeof(int32_t)));
-    if (S == 1) {
-        h->d_cost = h->d_cost_bs;
-        h->d_status = h->d_status_bs;
-    } else {
-        VP_TRY(hipMalloc((void **)&h->d_cost, (size_t)B * sizeof(double)));
-        VP_TRY(hipMalloc((void **)&h->d_status, (size_t)B * sizeof(int32_t)));
-    }
-    VP_TRY(hipMalloc((void **)&h->d_report, (size_t)B * sizeof(vp_report)));
-    VP_TRY(hipMalloc((void **)&h->d_sum4, 4 * sizeof(double)));
-    VP_TRY(hipMalloc((void **)&h->d_queue, sizeof(int)));
-    if (kern->uses_gen_ws && !ext) {
-        // (caller-evaluated models allocate it on first use: their resident kernels -- vp_ext.hpp -- need none)
-        if (int rc = ensure_gen_ws(h)) {
-            vp_batch_destroy(h);
-            return rc;
-        }
-    }
-    VP_TRY(hipEventCreate(&h->ev0));
-    VP_TRY(hipEventCreate(&h->ev1));
-    if (S > 1 && kern->mrhs_factor && kern->mrhs_stream && kern->mrhs_lm && kern->mrhs_finish) {
-        const int n_ = h->n, p_ = h->p, q_ = h->q;
-        VP_TRY(hipMalloc(&h->mrhs.qthin, (size_t)B * n_ * m * ts));
-        VP_TRY(hipMalloc(&h->mrhs.g, (size_t)B * std::max(1, p_) * m * ts));
-        VP_TRY(hipMalloc((void **)&h->mrhs.small, (size_t)B * mrhs_small_stride_rt(n_, p_) * sizeof(double)));
-        VP_TRY(hipMalloc((void **)&h->mrhs.statusA, (size_t)B * sizeof(int32_t)));
-        // partial-sum slots of the MODE 0 pass (the only writer): gx is fixed per handle -- min(ceil(S/8), the kernel set's
-        // cap) -- not the upper bound VP_MRHS_GX_MAX (B = 70000, S = 2 needs 1 slot per problem, not 512)
-        const int gx_acc = mrhs_gx(S, kern->mrhs_gx_cap > 0 ? kern->mrhs_gx_cap : 256);
-        if (gx_acc > VP_MRHS_GX_MAX) {
-            vp_batch_destroy(h);
-            return fail(VP_ERR_INVALID, "internal: partial-sum slots per problem exceed VP_MRHS_GX_MAX");
-        }
-        VP_TRY(hipMalloc((void **)&h->mrhs.acc, (size_t)B * gx_acc * (1 + n_ * n_ + p_) * sizeof(double)));
-        VP_TRY(hipMalloc(&h->mrhs.lm_state, (size_t)B * kern->mrhs_state_bytes));
-        VP_TRY(hipMalloc((void **)&h->mrhs.nactive, 2 * sizeof(int32_t)));
-        VP_TRY(hipMalloc((void **)&h->mrhs.done, (size_t)B * sizeof(int32_t)));
-        VP_TRY(hipMemsetAsync(h->mrhs.done, 0, (size_t)B * sizeof(int32_t), h->stream));
-        VP_TRY(hipMalloc(&h->mrhs.alpha_trial, (size_t)std::max<int64_t>(1, B * q_) * ts));
-        for (int i = 0; i < 2; ++i) {
-            VP_TRY(hipMalloc(&h->mrhs.cbuf[i], (size_t)B * S * n_ * ts));
-            VP_TRY(hipMalloc((void **)&h->mrhs.costbuf[i], (size_t)B * S * sizeof(double)));
-            VP_TRY(hipMalloc((void **)&h->mrhs.stbuf[i], (size_t)B * S * sizeof(int32_t)));
-        }
-        VP_TRY(hipMalloc((void **)&h->mrhs.widx, (size_t)B * sizeof(int32_t)));
-        VP_TRY(hipMalloc((void **)&h->mrhs.bidx, (size_t)B * sizeof(int32_t)));
-        VP_TRY(hipMalloc((void **)&h->mrhs.jcond, (size_t)B * sizeof(double)));
-        VP_TRY(hipMemsetAsync(h->mrhs.jcond, 0, (size_t)B * sizeof(double), h->stream));
-        h->have_mrhs = true;
-    }
-#undef VP_TRY
-    for (int k = 0; k < 3; ++k) h->last_ms[k] = -1.f;
     *out = h;
     return VP_ERR_OK;
 }
@@ -1201,61 +1346,10 @@ void vp_batch_destroy(vp_batch *h) {
     DeviceGuard dev_guard__;
     (void)dev_guard__.enter(h->device);
     (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(h->d_mrhs_tot);
-    (void)hipFree(h->d_gen_lm);
-    (void)hipFree(h->d_gen_nactive);
-    (void)hipFree(h->d_t);
-    (void)hipFree(h->d_w);
-    (void)hipFree(h->d_yw);
-    (void)hipFree(h->d_alpha);
-    (void)hipFree(h->d_C);
-    (void)hipFree(h->d_R);
-    (void)hipFree(h->d_cost_bs);
-    (void)hipFree(h->d_status_bs);
-    if (h->S != 1) {
-        (void)hipFree(h->d_cost);
-        (void)hipFree(h->d_status);
-    }
-    (void)hipFree(h->d_report);
-    (void)hipFree(h->d_sum4);
-    (void)hipFree(h->d_queue);
-    (void)hipFree(h->d_gen_ws);
-    (void)hipFree(h->tmp_a);
-    (void)hipFree(h->tmp_b);
-    (void)hipFree(h->ext_phi_own);
-    (void)hipFree(h->ext_dphi_own);
-    (void)hipFree(h->d_xf_state);
-    (void)hipFree(h->d_xf_trial);
-    (void)hipFree(h->d_xf_want);
-    (void)hipFree(h->d_xf_nactive);
-    (void)hipFree(h->d_xf_ctrial);
-    (void)hipFree(h->d_xf_active);
-    (void)hipFree(h->d_rescue);
-    (void)hipFree(h->d_rescue_ws);
-    if (h->h_xf_nactive) (void)hipHostFree(h->h_xf_nactive);
-    // (the struct is zero-initialised: freeing unconditionally also covers a create that failed half way)
-    (void)hipFree(h->mrhs.qthin);
-    (void)hipFree(h->mrhs.g);
-    (void)hipFree(h->mrhs.small);
-    (void)hipFree(h->mrhs.statusA);
-    (void)hipFree(h->mrhs.done);
-    (void)hipFree(h->mrhs.acc);
-    (void)hipFree(h->mrhs.lm_state);
-    (void)hipFree(h->mrhs.nactive);
-    (void)hipFree(h->mrhs.alpha_trial);
-    for (int i = 0; i < 2; ++i) {
-        (void)hipFree(h->mrhs.cbuf[i]);
-        (void)hipFree(h->mrhs.costbuf[i]);
-        (void)hipFree(h->mrhs.stbuf[i]);
-    }
-    (void)hipFree(h->mrhs.widx);
-    (void)hipFree(h->mrhs.jcond);
-    (void)hipFree(h->mrhs.bidx);
-    if (h->mrhs_graph) (void)hipGraphExecDestroy(h->mrhs_graph);
-    if (h->mrhs_graph_tail) (void)hipGraphExecDestroy(h->mrhs_graph_tail);
-    if (h->h_nactive) (void)hipHostFree(h->h_nactive);
-    if (h->h_io) (void)hipHostFree(h->h_io);
-    if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
+    for (void *mem : h->owned_dev) (void)hipFree(mem);
+    for (void *mem : h->owned_pinned) (void)hipHostFree(mem);
+    h->graphs.drop();
+    if (h->graphs.cap_stream) (void)hipStreamDestroy(h->graphs.cap_stream);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -1279,20 +1373,30 @@ static int ext_stage(vp_batch *h, const void *user, int64_t cols, const void *&d
         return 0;
     }
     const size_t bytes = (size_t)h->B * (size_t)cols * (size_t)(h->m_user ? h->m_user : h->m) * tsize(h->dtype);
-    if (!own) VP_HIP(hipMalloc(&own, bytes ? bytes : 1));
+    if (int rc = h->ensure(own, bytes ? bytes : 1)) return rc;
     VP_HIP(hipMemcpyAsync(own, user, bytes, hipMemcpyHostToDevice, h->stream));
     dev = own;
     return 0;
 }
 
-int vp_set_params_with_basis(vp_batch *h, const void *alpha, const void *Phi, const void *dPhi) {
-    VP_ENTER(h);
-    if (!h->external) return fail(VP_ERR_UNSUPPORTED, "vp_set_params_with_basis needs a handle made by vp_batch_create_external");
-    if (!alpha || !Phi) return fail(VP_ERR_INVALID, "null alpha / Phi");
-    VP_HIP(hipMemcpyAsync(h->d_alpha, alpha, (size_t)h->B * h->q * tsize(h->dtype),
-                          device_ptrs(h) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    if (int rc = ext_stage(h, Phi, h->n, h->ext_phi, h->ext_phi_own)) return rc;
-    if (int rc = ext_stage(h, dPhi, h->ext_np, h->ext_dphi, h->ext_dphi_own)) return rc;
+static int copy_status(vp_batch *h, int32_t *status);
+
+// everything of one evaluation at d_alpha into the caller's arrays (each may be null): vp_evaluate, vp_evaluate_with_basis
+static int evaluate_at_alpha(vp_batch *h, void *r_out, void *J_out, void *C_out, double *cost_out, int32_t *status) {
+    RowOut r, J;
+    if (int rc = r.init(h, r_out, (size_t)h->B * h->S)) return rc;
+    if (int rc = J.init(h, J_out, (size_t)h->B * h->q * h->S)) return rc;
+    if (int rc = run_evaluate(h, r.dptr, J.dptr, h->d_C)) return rc;
+    h->have_params = true;
+    h->r_valid = false;
+    if (int rc = r.finish(h)) return rc;
+    if (int rc = J.finish(h)) return rc;
+    if (int rc = copy_out(h, C_out, h->d_C, (size_t)h->B * h->S * h->n * tsize(h->dtype))) return rc;
+    if (int rc = copy_out(h, cost_out, h->d_cost, (size_t)h->B * sizeof(double))) return rc;
+    return copy_status(h, status);
+}
+// the residual cache and the coefficients at d_alpha: vp_set_params, vp_set_params_with_basis
+static int cache_at_alpha(vp_batch *h) {
     if (int rc = ensure_R(h)) return rc;
     if (int rc = run_evaluate(h, h->d_R, nullptr, h->d_C)) return rc;
     h->have_params = true;
@@ -1301,7 +1405,15 @@ int vp_set_params_with_basis(vp_batch *h, const void *alpha, const void *Phi, co
     return VP_ERR_OK;
 }
 
-static int copy_status(vp_batch *h, int32_t *status);
+int vp_set_params_with_basis(vp_batch *h, const void *alpha, const void *Phi, const void *dPhi) {
+    VP_ENTER(h);
+    if (!h->external) return fail(VP_ERR_UNSUPPORTED, "vp_set_params_with_basis needs a handle made by vp_batch_create_external");
+    if (!alpha || !Phi) return fail(VP_ERR_INVALID, "null alpha / Phi");
+    if (int rc = upload_alpha(h, alpha)) return rc;
+    if (int rc = ext_stage(h, Phi, h->n, h->ext_phi, h->ext_phi_own)) return rc;
+    if (int rc = ext_stage(h, dPhi, h->ext_np, h->ext_dphi, h->ext_dphi_own)) return rc;
+    return cache_at_alpha(h);
+}
 
 int vp_jacobian_with_derivatives(vp_batch *h, const void *dPhi, void *J_out, int32_t *status) {
     VP_ENTER(h);
@@ -1318,22 +1430,10 @@ int vp_evaluate_with_basis(vp_batch *h, const void *alpha, const void *Phi, cons
     if (!h->external) return fail(VP_ERR_UNSUPPORTED, "vp_evaluate_with_basis needs a handle made by vp_batch_create_external");
     if (!alpha || !Phi) return fail(VP_ERR_INVALID, "null alpha / Phi");
     if (J_out && !dPhi && h->ext_np > 0) return fail(VP_ERR_INVALID, "a Jacobian needs the derivative columns dPhi");
-    const size_t ts = tsize(h->dtype);
-    VP_HIP(hipMemcpyAsync(h->d_alpha, alpha, (size_t)h->B * h->q * ts,
-                          device_ptrs(h) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    if (int rc = upload_alpha(h, alpha)) return rc;
     if (int rc = ext_stage(h, Phi, h->n, h->ext_phi, h->ext_phi_own)) return rc;
     if (int rc = ext_stage(h, dPhi, h->ext_np, h->ext_dphi, h->ext_dphi_own)) return rc;
-    RowOut r, J;
-    if (int rc = r.init(h, r_out, (size_t)h->B * h->S)) return rc;
-    if (int rc = J.init(h, J_out, (size_t)h->B * h->q * h->S)) return rc;
-    if (int rc = run_evaluate(h, r.dptr, J.dptr, h->d_C)) return rc;
-    h->have_params = true;
-    h->r_valid = false;
-    if (int rc = r.finish(h)) return rc;
-    if (int rc = J.finish(h)) return rc;
-    if (int rc = copy_out(h, C_out, h->d_C, (size_t)h->B * h->S * h->n * ts)) return rc;
-    if (int rc = copy_out(h, cost_out, h->d_cost, (size_t)h->B * sizeof(double))) return rc;
-    if (int rc = copy_status(h, status)) return rc;
+    if (int rc = evaluate_at_alpha(h, r_out, J_out, C_out, cost_out, status)) return rc;
     if (!device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream));
     return VP_ERR_OK;
 }
@@ -1353,43 +1453,35 @@ int vp_fit_begin(vp_batch *h, const vp_lm_opts *opts, const void *alpha0, int fl
     const size_t ts = tsize(h->dtype);
     if (external_fit_generic(h->dtype, h->n, h->ext_np, h->q, h->m, h->S)) {
         // shapes outside the specialised tables / several right-hand sides: the generic step and its workspace
-        if (!h->d_gen_ws) {
-            const size_t slot = (size_t)(h->n + 1 + h->ext_np + h->q) * (size_t)h->m * ts;
-            int64_t blocks = std::min<int64_t>(h->B, 1024);
-            while (blocks > 1 && (size_t)blocks * slot > ((size_t)4 << 30)) blocks /= 2;
-            h->gen_blocks = (int)blocks;
-            VP_HIP(hipMalloc(&h->d_gen_ws, (size_t)blocks * slot));
-        }
-        if (h->S > 1 && !h->d_xf_ctrial) VP_HIP(hipMalloc(&h->d_xf_ctrial, (size_t)h->B * h->S * h->n * ts));
+        if (int rc = alloc_gen_ws(h, h->B)) return rc; // (h->p == h->ext_np: one workspace slot per problem in flight)
+        if (h->S > 1)
+            if (int rc = h->ensure(h->d_xf_ctrial, (size_t)h->B * h->S * h->n * ts)) return rc;
     }
     // (each buffer guarded on its own: an allocation that fails half way leaves the handle in a state the next call completes)
-    if (!h->d_xf_state) VP_HIP(hipMalloc(&h->d_xf_state, (size_t)h->B * rec + 16));
-    if (!h->d_xf_trial) VP_HIP(hipMalloc(&h->d_xf_trial, (size_t)h->B * h->q * ts));
-    if (!h->d_xf_want) VP_HIP(hipMalloc((void **)&h->d_xf_want, (size_t)h->B * sizeof(int32_t)));
-    if (!h->d_xf_nactive) VP_HIP(hipMalloc((void **)&h->d_xf_nactive, 2 * sizeof(int32_t)));
-    if (!h->h_xf_nactive) VP_HIP(hipHostMalloc((void **)&h->h_xf_nactive, sizeof(int32_t), hipHostMallocDefault));
+    if (int rc = h->ensure(h->d_xf_state, (size_t)h->B * rec + 16)) return rc;
+    if (int rc = h->ensure(h->d_xf_trial, (size_t)h->B * h->q * ts)) return rc;
+    if (int rc = h->ensure(h->d_xf_want, (size_t)h->B * sizeof(int32_t))) return rc;
+    if (int rc = h->ensure(h->d_xf_nactive, 2 * sizeof(int32_t))) return rc;
+    if (!h->h_xf_nactive)
+        if (int rc = h->alloc_pinned(h->h_xf_nactive, sizeof(int32_t), hipHostMallocDefault)) return rc;
     if (!h->d_xf_active) {
         // both lists start as the identity: an entry beyond a step's count is then always a valid (finished) problem index
-        VP_HIP(hipMalloc((void **)&h->d_xf_active, (size_t)2 * h->B * sizeof(int32_t)));
+        if (int rc = h->alloc(h->d_xf_active, (size_t)2 * h->B * sizeof(int32_t))) return rc;
         std::vector<int32_t> iota((size_t)2 * h->B);
         for (int64_t i = 0; i < 2 * h->B; ++i) iota[(size_t)i] = (int32_t)(i % h->B);
         VP_HIP(hipMemcpyAsync(h->d_xf_active, iota.data(), iota.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
         VP_HIP(hipStreamSynchronize(h->stream));
     }
     h->xf_known_active = h->B;
-    if (opts) h->xf_opts = *opts;
-    else vp_lm_opts_default(&h->xf_opts, h->dtype);
-    VP_HIP(hipMemcpyAsync(h->d_alpha, alpha0, (size_t)h->B * h->q * ts,
-                          device_ptrs(h) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    h->xf_opts = opts_or_default(h, opts);
+    if (int rc = upload_alpha(h, alpha0)) return rc;
     if (!device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream));
     VP_HIP(hipMemsetAsync(h->d_xf_nactive, 0, 2 * sizeof(int32_t), h->stream));
     h->xf_running = true;
     h->xf_init = true;
     h->xf_flags = flags;
     h->xf_steps = 0;
-    h->have_params = false;
-    h->r_valid = false;
-    h->have_report = false;
+    invalidate(h);
     return VP_ERR_OK;
 }
 
@@ -1406,42 +1498,9 @@ int vp_fit_step_with_basis(vp_batch *h, const void *Phi, const void *dPhi, void 
     const size_t ts = tsize(h->dtype);
     const bool direct = device_ptrs(h); // the kernel writes the caller's device arrays itself
     ExtFitParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.dtype = h->dtype;
-    p.n = h->n;
-    p.q = h->q;
-    p.np = h->ext_np;
-    p.m = h->m;
-    p.B = h->B;
-    p.phi = h->ext_phi;
-    p.dphi = h->ext_dphi;
-    p.w = h->d_w;
-    p.yw = h->d_yw;
-    p.w_stride = (h->flags & VP_FLAG_W_PER_PROBLEM) ? h->m : 0;
-    p.state = h->d_xf_state;
-    p.alpha0 = h->d_alpha;
-    p.alpha_best = h->d_alpha;
-    p.C_best = h->d_C;
-    p.cost = h->d_cost;
-    p.status = h->d_status;
-    p.report = h->d_report;
+    fill_ext_params(h, p);
     p.alpha_trial = (direct && alpha_trial_out) ? alpha_trial_out : h->d_xf_trial;
     p.want = (direct && want_out) ? want_out : h->d_xf_want;
-    p.nactive = h->d_xf_nactive;
-    p.step = (int)(h->xf_steps & 1);
-    p.pb = h->ext_pb;
-    p.pp = h->ext_pp;
-    p.eps = h->eps;
-    p.opts = h->xf_opts;
-    p.init = h->xf_init ? 1 : 0;
-    p.lazy = lazy ? 1 : 0;
-    p.S = h->S;
-    p.gen_ws = h->d_gen_ws;
-    p.gen_blocks = h->gen_blocks;
-    p.C_trial = h->d_xf_ctrial;
-    p.active_lists = h->d_xf_active;
-    p.known_active = h->xf_known_active;
-    p.stream = h->stream;
     Timer tm(h, VP_KERNEL_FIT);
     const int rc = external_fit_step(p);
     tm.stop();
@@ -1479,33 +1538,20 @@ int vp_fit_end(vp_batch *h, void *alpha_out, void *C_out, vp_report *rep) {
     VP_ENTER(h);
     if (!h->external || !h->xf_running) return fail(VP_ERR_INVALID, "vp_fit_end without vp_fit_begin");
     if (h->xf_init) return fail(VP_ERR_INVALID, "vp_fit_end before the first vp_fit_step_with_basis");
-    const size_t ts = tsize(h->dtype);
     h->xf_running = false;
-    h->have_params = true;
-    h->r_valid = false;
-    h->have_report = true;
+    after_fit(h);
     // the columns the handle last saw belong to a trial point, not necessarily to the fitted one
     h->ext_phi = nullptr;
     h->ext_dphi = nullptr;
-    if (int rc = copy_out(h, alpha_out, h->d_alpha, (size_t)h->B * h->q * ts)) return rc;
-    if (int rc = copy_out(h, C_out, h->d_C, (size_t)h->B * h->S * h->n * ts)) return rc;
-    if (int rc = copy_out(h, rep, h->d_report, (size_t)h->B * sizeof(vp_report))) return rc;
-    return VP_ERR_OK;
+    return copy_fit_out(h, alpha_out, C_out, rep);
 }
 
 int vp_set_params(vp_batch *h, const void *alpha) {
     VP_ENTER(h);
     VP_NOT_EXTERNAL(h, "vp_set_params");
     if (!alpha) return fail(VP_ERR_INVALID, "null alpha");
-    const size_t bytes = (size_t)h->B * h->q * tsize(h->dtype);
-    VP_HIP(hipMemcpyAsync(h->d_alpha, alpha, bytes, device_ptrs(h) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                          h->stream));
-    if (int rc = ensure_R(h)) return rc;
-    if (int rc = run_evaluate(h, h->d_R, nullptr, h->d_C)) return rc;
-    h->have_params = true;
-    h->r_valid = true;
-    if (!device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream));
-    return VP_ERR_OK;
+    if (int rc = upload_alpha(h, alpha)) return rc;
+    return cache_at_alpha(h);
 }
 
 int vp_params(vp_batch *h, void *alpha_out) {
@@ -1575,42 +1621,22 @@ int vp_set_observations(vp_batch *h, const void *Y) {
     const size_t y_elems = (size_t)h->B * h->S * h->m;
     // Y_w = W * Y straight into the handle's buffer; host pointers are staged through the buffer itself
     const void *ysrc = Y;
-    std::vector<char> ypad;
-    if (h->m_user) { // m < n: pad the caller's rows on the host (tiny by construction), then as a host array
-        const size_t nb = (size_t)h->B * h->S;
-        std::vector<char> yh(nb * h->m_user * ts);
-        if (device_ptrs(h)) {
-            VP_HIP(hipMemcpyAsync(yh.data(), Y, yh.size(), hipMemcpyDeviceToHost, h->stream));
-            VP_HIP(hipStreamSynchronize(h->stream));
-        } else {
-            std::memcpy(yh.data(), Y, yh.size());
-        }
-        ypad.resize(y_elems * ts);
-        pad_rows_host(yh.data(), ypad.data(), nb, h->m_user, h->m, ts, 0.0);
-        VP_HIP(hipMemcpyAsync(h->d_yw, ypad.data(), y_elems * ts, hipMemcpyHostToDevice, h->stream));
+    PaddedInputs pad;
+    if (h->m_user) { // m < n: pad the caller's rows on the host, then as a host array
+        if (int rc = pad_inputs_host(pad, device_ptrs(h), h->stream, ts, h->m_user, h->m, nullptr, 0, Y, (size_t)h->B * h->S,
+                                     nullptr, 0, false))
+            return rc;
+        VP_HIP(hipMemcpyAsync(h->d_yw, pad.y.data(), y_elems * ts, hipMemcpyHostToDevice, h->stream));
         VP_HIP(hipStreamSynchronize(h->stream));
         ysrc = h->d_yw;
     } else if (!device_ptrs(h)) {
         VP_HIP(hipMemcpyAsync(h->d_yw, Y, y_elems * ts, hipMemcpyHostToDevice, h->stream));
         ysrc = h->d_yw; // in place: every element is read once and written once by the same thread
     }
-    if (h->d_w || ysrc != h->d_yw) {
-        const int64_t total = (int64_t)y_elems;
-        const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 65536);
-        const int64_t wstride = (h->flags & VP_FLAG_W_PER_PROBLEM) ? h->m : 0;
-        if (h->dtype == VP_F64)
-            hipLaunchKernelGGL(weight_data_kernel<double>, dim3(grid), dim3(256), 0, h->stream, (const double *)ysrc,
-                               (const double *)h->d_w, (double *)h->d_yw, (int)h->m, h->S, wstride, total);
-        else
-            hipLaunchKernelGGL(weight_data_kernel<float>, dim3(grid), dim3(256), 0, h->stream, (const float *)ysrc,
-                               (const float *)h->d_w, (float *)h->d_yw, (int)h->m, h->S, wstride, total);
-        VP_HIP(hipGetLastError());
-    }
+    if (h->d_w || ysrc != h->d_yw)
+        if (int rc = launch_weight_data(h, ysrc)) return rc;
     if (!device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream)); // the caller may reuse its host buffer
-    // the cached evaluation / fit belongs to the old data
-    h->have_params = false;
-    h->r_valid = false;
-    h->have_report = false;
+    invalidate(h); // the cached evaluation / fit belongs to the old data
     return VP_ERR_OK;
 }
 
@@ -1625,20 +1651,8 @@ int vp_evaluate(vp_batch *h, const void *alpha, void *r_out, void *J_out, void *
     VP_ENTER(h);
     VP_NOT_EXTERNAL(h, "vp_evaluate");
     if (!alpha) return fail(VP_ERR_INVALID, "null alpha");
-    const size_t ts = tsize(h->dtype);
-    VP_HIP(hipMemcpyAsync(h->d_alpha, alpha, (size_t)h->B * h->q * ts,
-                          device_ptrs(h) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    RowOut r, J;
-    if (int rc = r.init(h, r_out, (size_t)h->B * h->S)) return rc;
-    if (int rc = J.init(h, J_out, (size_t)h->B * h->q * h->S)) return rc;
-    if (int rc = run_evaluate(h, r.dptr, J.dptr, h->d_C)) return rc;
-    h->have_params = true;
-    h->r_valid = false;
-    if (int rc = r.finish(h)) return rc;
-    if (int rc = J.finish(h)) return rc;
-    if (int rc = copy_out(h, C_out, h->d_C, (size_t)h->B * h->S * h->n * ts)) return rc;
-    if (int rc = copy_out(h, cost_out, h->d_cost, (size_t)h->B * sizeof(double))) return rc;
-    return copy_status(h, status);
+    if (int rc = upload_alpha(h, alpha)) return rc;
+    return evaluate_at_alpha(h, r_out, J_out, C_out, cost_out, status);
 }
 
 int vp_basis(vp_batch *h, const void *alpha, void *Phi_out, void *dPhi_out, int flags) {
@@ -1686,14 +1700,11 @@ constexpr int kRescueBlocks = 8;
 int rescue_prepare(vp_batch *h, LaunchParams &p) {
     if (h->rescue_off || h->kern->family == FAMILY_GENERIC || h->kern->gram_fit) return 0; // (the generic kernel scales by itself)
     if (!h->d_rescue) {
-        VP_HIP(hipMalloc((void **)&h->d_rescue, (size_t)(2 + h->B) * sizeof(int32_t)));
+        if (int rc = h->alloc(h->d_rescue, (size_t)(2 + h->B) * sizeof(int32_t))) return rc;
         VP_HIP(hipMemsetAsync(h->d_rescue, 0, 2 * sizeof(int32_t), h->stream));
         h->rescue_slot = 0;
     }
-    if (!h->d_rescue_ws) {
-        const size_t slot = (size_t)(h->n + 1 + h->p + h->q) * (size_t)h->m * tsize(h->dtype);
-        VP_HIP(hipMalloc(&h->d_rescue_ws, (size_t)kRescueBlocks * slot));
-    }
+    if (int rc = h->ensure(h->d_rescue_ws, (size_t)kRescueBlocks * gen_slot_bytes(h))) return rc;
     p.rescue = h->d_rescue;
     p.rescue_slot = h->rescue_slot;
     return 0;
@@ -1730,35 +1741,22 @@ int vp_fit_trace(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C
     if (h->m_user && (int64_t)h->q > h->m_user * h->S) {
         // m < n AND fewer residuals than nonlinear parameters (the padded handle would count its own n rows): the reference's
         // LM driver evaluates once and reports WrongDimensions
-        const size_t ts = tsize(h->dtype);
-        VP_HIP(hipMemcpyAsync(h->d_alpha, alpha_inout, (size_t)h->B * h->q * ts,
-                              device_ptrs(h) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+        if (int rc = upload_alpha(h, alpha_inout)) return rc;
         if (int rc = run_evaluate(h, nullptr, nullptr, h->d_C)) return rc;
-        OutBuf trw;
-        if (trace_out && trace_rows > 0) { // rows never written read as NaN; row 0 = the initial point (ratio = NaN)
-            const size_t trb = (size_t)h->B * (size_t)trace_rows * (h->q + 4) * sizeof(double);
-            if (int rc = trw.init(h, trace_out, trb)) return rc;
-            VP_HIP(hipMemsetAsync(trw.dptr, 0xFF, trb, h->stream));
-        }
+        OutBuf trw; // row 0 = the initial point (ratio = NaN)
+        if (int rc = trace_begin(h, trw, trace_out, trace_rows)) return rc;
         hipLaunchKernelGGL(wrong_dimensions_report_kernel, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream,
                            (const double *)h->d_cost, (const int32_t *)h->d_status, h->B, h->d_report,
                            trw.dptr ? (double *)trw.dptr : nullptr, trace_rows, h->q, h->dtype, (const void *)h->d_alpha);
         VP_HIP(hipGetLastError());
-        h->have_params = true;
-        h->r_valid = false;
-        h->have_report = true;
-        if (int rc = copy_out(h, C_out, h->d_C, (size_t)h->B * h->S * h->n * ts)) return rc;
-        if (int rc = copy_out(h, rep, h->d_report, (size_t)h->B * sizeof(vp_report))) return rc;
+        after_fit(h);
+        if (int rc = copy_fit_out(h, nullptr, C_out, rep)) return rc; // (the parameters stay the caller's)
         return trw.finish(h);
     }
     if (h->S != 1) return mrhs_fit(h, opts, alpha_inout, C_out, rep, trace_out, trace_rows);
     if (!h->kern->fit && !h->kern->fit_single) return fail(VP_ERR_UNSUPPORTED, "no fit kernel for this model");
-    vp_lm_opts o;
-    if (opts) o = *opts;
-    else vp_lm_opts_default(&o, h->dtype);
-    const size_t ts = tsize(h->dtype);
-    VP_HIP(hipMemcpyAsync(h->d_alpha, alpha_inout, (size_t)h->B * h->q * ts,
-                          device_ptrs(h) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    const vp_lm_opts o = opts_or_default(h, opts);
+    if (int rc = upload_alpha(h, alpha_inout)) return rc;
     LaunchParams p;
     fill_params(h, p);
     p.alpha_out = h->d_alpha;
@@ -1768,13 +1766,8 @@ int vp_fit_trace(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C
     p.report = h->d_report;
     p.opts = &o;
     OutBuf tr;
-    const size_t tr_bytes = (size_t)h->B * (size_t)(trace_rows > 0 ? trace_rows : 0) * (h->q + 4) * sizeof(double);
-    if (trace_out && trace_rows > 0) {
-        if (int rc = tr.init(h, trace_out, tr_bytes)) return rc;
-        VP_HIP(hipMemsetAsync(tr.dptr, 0xFF, tr_bytes, h->stream)); // NaN-fill: unused rows read as NaN
-        p.trace = (double *)tr.dptr;
-        p.trace_rows = trace_rows;
-    }
+    if (int rc = trace_begin(h, tr, trace_out, trace_rows)) return rc;
+    set_trace(p, tr, trace_rows);
     // kern->fit is the persistent slot kernel (vp_fit2.hpp); it falls back to the one-problem-per-wave kernel
     // (vp_fit.hpp) by itself for the cases it does not cover (weights, per-problem grids, models without a trailing
     // constant column, batches smaller than the device's resident wave slots).  vp_set_fit_kernel overrides.
@@ -1787,14 +1780,9 @@ int vp_fit_trace(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C
     if (rc == VP_ERR_OK && list_used) rc = rescue_refit(h, p); // (the problems the fit kernel flagged and did not re-fit itself)
     tm.stop();
     if (rc != VP_ERR_OK) return fail(rc, "fit kernel launch failed");
-    h->have_params = true;
-    h->r_valid = false;
-    h->have_report = true;
-    if (int rc2 = copy_out(h, alpha_inout, h->d_alpha, (size_t)h->B * h->q * ts)) return rc2;
-    if (int rc2 = copy_out(h, C_out, h->d_C, (size_t)h->B * h->n * ts)) return rc2;
-    if (int rc2 = copy_out(h, rep, h->d_report, (size_t)h->B * sizeof(vp_report))) return rc2;
-    if (int rc2 = tr.finish(h)) return rc2;
-    return VP_ERR_OK;
+    after_fit(h);
+    if (int rc2 = copy_fit_out(h, alpha_inout, C_out, rep)) return rc2;
+    return tr.finish(h);
 }
 
 int vp_debug_set_refit(vp_batch *h, int enabled) {
@@ -1814,8 +1802,7 @@ int vp_debug_gram_evaluate(vp_batch *h, const void *alpha, double *out) {
     if (int rc = a.init(h, alpha, (size_t)h->B * h->q * ts)) return rc;
     OutBuf o;
     if (int rc = o.init(h, out, (size_t)h->B * per * sizeof(double))) return rc;
-    vp_lm_opts opt;
-    vp_lm_opts_default(&opt, h->dtype);
+    const vp_lm_opts opt = opts_or_default(h, nullptr);
     LaunchParams p;
     fill_params(h, p);
     p.alpha_out = const_cast<void *>(a.dptr); // read only in this mode
@@ -1866,10 +1853,13 @@ int vp_debug_lmpar_gram(int64_t B, int q, const double *Rj, const int32_t *ipvt,
     const size_t sizes[7] = {nq * q * sizeof(double), nq * sizeof(int32_t), nq * sizeof(double), nq * sizeof(double),
                              (size_t)B * sizeof(double), (size_t)B * sizeof(double), (size_t)B * (q + 2) * sizeof(double)};
     const void *src[6] = {Rj, ipvt, diag, qtb, delta, par_in};
+    DevMem mem[7];
     void *d[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int rc = VP_ERR_OK;
-    for (int i = 0; i < 7 && rc == VP_ERR_OK; ++i)
-        if (hipMalloc(&d[i], sizes[i]) != hipSuccess) rc = VP_ERR_HIP;
+    for (int i = 0; i < 7 && rc == VP_ERR_OK; ++i) {
+        if (mem[i].alloc(sizes[i]) != 0) rc = VP_ERR_HIP;
+        d[i] = mem[i].p;
+    }
     for (int i = 0; i < 6 && rc == VP_ERR_OK; ++i)
         if (hipMemcpy(d[i], src[i], sizes[i], hipMemcpyHostToDevice) != hipSuccess) rc = VP_ERR_HIP;
     if (rc == VP_ERR_OK) {
@@ -1884,8 +1874,6 @@ int vp_debug_lmpar_gram(int64_t B, int q, const double *Rj, const int32_t *ipvt,
         else go(std::integral_constant<int, 5>());
         if (hipGetLastError() != hipSuccess || hipMemcpy(out, d[6], sizes[6], hipMemcpyDeviceToHost) != hipSuccess) rc = VP_ERR_HIP;
     }
-    for (int i = 0; i < 7; ++i)
-        if (d[i]) (void)hipFree(d[i]);
     return rc == VP_ERR_OK ? VP_ERR_OK : fail(rc, "vp_debug_lmpar_gram: HIP call failed");
 }
 
@@ -1929,17 +1917,13 @@ int vp_statistics(vp_batch *h, void *cov_out, double *reduced_chi2_out, void *co
     if (!cov_out || !reduced_chi2_out) return fail(VP_ERR_INVALID, "null output");
     const size_t ts = tsize(h->dtype);
     const int k = h->n + h->q;
-    OutBuf cov, chi2, st;
+    OutBuf cov, chi2;
     RowOut sig;
+    StatusOut st; // (declared last: its temporary is the first to go)
     if (int rc = cov.init(h, cov_out, (size_t)h->B * k * k * ts)) return rc;
     if (int rc = chi2.init(h, reduced_chi2_out, (size_t)h->B * sizeof(double))) return rc;
     if (int rc = sig.init(h, conf_sigma_out, (size_t)h->B)) return rc;
-    void *st_tmp = nullptr;
-    int32_t *st_dev = status && device_ptrs(h) ? status : nullptr;
-    if (!st_dev) {
-        VP_HIP(hipMalloc(&st_tmp, (size_t)h->B * sizeof(int32_t)));
-        st_dev = (int32_t *)st_tmp;
-    }
+    if (int rc = st.init(h, status)) return rc;
     LaunchParams p;
     fill_params(h, p);
     p.C_out = h->d_C;
@@ -1948,17 +1932,12 @@ int vp_statistics(vp_batch *h, void *cov_out, double *reduced_chi2_out, void *co
     p.Phi_out = cov.dptr;
     p.dPhi_out = chi2.dptr;
     p.r_out = sig.dptr;
-    p.J_out = st_dev;
+    p.J_out = st.dev;
     int rc = h->kern->stats(p);
     if (rc == VP_ERR_OK) rc = cov.finish(h);
     if (rc == VP_ERR_OK) rc = chi2.finish(h);
     if (rc == VP_ERR_OK) rc = sig.finish(h);
-    if (rc == VP_ERR_OK && status && !device_ptrs(h)) {
-        hipError_t e = hipMemcpyAsync(status, st_dev, (size_t)h->B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = VP_ERR_HIP;
-    }
-    if (st_tmp) (void)hipFree(st_tmp);
+    if (rc == VP_ERR_OK) rc = st.finish(h, status);
     if (rc != VP_ERR_OK) return fail(rc, "statistics kernel failed");
     return VP_ERR_OK;
 }
@@ -2022,21 +2001,13 @@ int vp_global_statistics(vp_batch *h, void *cov_alpha_out, double *reduced_chi2_
     if (int rc = cc.init(h, coef_cov_out, (size_t)B * S * n * n * ts)) return rc;
     if (int rc = ca.init(h, coef_alpha_cov_out, (size_t)B * S * n * q * ts)) return rc;
     if (int rc = sig.init(h, conf_sigma_out, (size_t)B * S)) return rc;
-    struct DevMem { // freed on every path (hipFree synchronises)
-        void *p = nullptr;
-        ~DevMem() {
-            if (p) (void)hipFree(p);
-        }
-    } ws, st_tmp;
+    DevMem ws; // freed on every path, after the status temporary and before the output staging
+    StatusOut st;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t sz_basis = h->external ? 0 : al((size_t)bc * (n + P) * m * ts), sz_cols = al((size_t)bc * (n + P) * m * 8),
                  sz_rows = band ? al((size_t)bc * (1 + n * (n + 1) / 2) * m * 8) : 0, sz_small = (size_t)bc * gs::kGsSmall * 8;
-    VP_HIP(hipMalloc(&ws.p, sz_basis + sz_cols + sz_rows + sz_small));
-    int32_t *st_dev = status && device_ptrs(h) ? status : nullptr;
-    if (!st_dev) {
-        VP_HIP(hipMalloc(&st_tmp.p, (size_t)B * sizeof(int32_t)));
-        st_dev = (int32_t *)st_tmp.p;
-    }
+    if (int rc = ws.alloc(sz_basis + sz_cols + sz_rows + sz_small)) return rc;
+    if (int rc = st.init(h, status)) return rc;
     char *wsb = (char *)ws.p;
     void *basis_ws = h->external ? nullptr : wsb;
     gp.ws_cols = (double *)(wsb + sz_basis);
@@ -2072,7 +2043,7 @@ int vp_global_statistics(vp_batch *h, void *cov_alpha_out, double *reduced_chi2_
         gp.coef_cov = cc.dptr ? (char *)cc.dptr + (size_t)b0 * S * n * n * ts : nullptr;
         gp.coef_alpha_cov = ca.dptr ? (char *)ca.dptr + (size_t)b0 * S * n * q * ts : nullptr;
         gp.band = sig.dptr ? (char *)sig.dptr + (size_t)b0 * S * m * ts : nullptr;
-        gp.status_out = st_dev + b0;
+        gp.status_out = st.dev + b0;
         if (int rc = gstats_launch(gp)) return fail(rc, "global statistics kernels failed");
     }
     if (int rc = cov.finish(h)) return rc;
@@ -2080,10 +2051,7 @@ int vp_global_statistics(vp_batch *h, void *cov_alpha_out, double *reduced_chi2_
     if (int rc = cc.finish(h)) return rc;
     if (int rc = ca.finish(h)) return rc;
     if (int rc = sig.finish(h)) return rc;
-    if (status && !device_ptrs(h)) {
-        VP_HIP(hipMemcpyAsync(status, st_dev, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        VP_HIP(hipStreamSynchronize(h->stream));
-    }
+    if (int rc = st.finish(h, status)) return rc;
     if (device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream)); // (the workspace is freed on return)
     return VP_ERR_OK;
 }
@@ -2091,13 +2059,8 @@ int vp_global_statistics(vp_batch *h, void *cov_alpha_out, double *reduced_chi2_
 int vp_summary(vp_batch *h, double out[4]) {
     VP_ENTER(h);
     if (!h->have_report) return fail(VP_ERR_INVALID, "vp_summary requires a completed vp_fit");
-    VP_HIP(hipMemsetAsync(h->d_sum4, 0, 4 * sizeof(double), h->stream));
-    const unsigned grid = (unsigned)std::min<int64_t>((h->B + 255) / 256, 1024);
-    hipLaunchKernelGGL(summary_kernel, dim3(grid), dim3(256), 0, h->stream, h->d_report, h->B, h->d_sum4);
-    VP_HIP(hipGetLastError());
-    VP_HIP(hipMemcpyAsync(out, h->d_sum4, 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    VP_HIP(hipStreamSynchronize(h->stream));
-    return VP_ERR_OK;
+    if (int rc = launch_summary(h, h->d_sum4)) return rc;
+    return read_sum4(h, out);
 }
 
 // cond(J D^-1) as the Gram-based LM step of the last global fit saw it at its worst (MrhsWs::jcond)
@@ -2114,11 +2077,7 @@ int vp_summary_device(vp_batch *h, double *dev_out4) {
     VP_ENTER(h);
     if (!h->have_report) return fail(VP_ERR_INVALID, "vp_summary_device requires a completed vp_fit");
     if (!dev_out4) return fail(VP_ERR_INVALID, "null output");
-    VP_HIP(hipMemsetAsync(dev_out4, 0, 4 * sizeof(double), h->stream));
-    const unsigned grid = (unsigned)std::min<int64_t>((h->B + 255) / 256, 1024);
-    hipLaunchKernelGGL(summary_kernel, dim3(grid), dim3(256), 0, h->stream, h->d_report, h->B, dev_out4);
-    VP_HIP(hipGetLastError());
-    return VP_ERR_OK;
+    return launch_summary(h, dev_out4);
 }
 
 // == the vp_reduce_cost of SURVEY.md 8(b): local aggregates + ONE RCCL all-reduce of 4 doubles on the handle's stream.
@@ -2144,19 +2103,14 @@ int vp_reduce_cost(vp_batch *h, void *rccl_comm, double out[4]) {
     VP_ENTER(h);
     if (!out) return fail(VP_ERR_INVALID, "null output");
     if (!h->have_report) return fail(VP_ERR_INVALID, "vp_reduce_cost requires a completed vp_fit");
-    VP_HIP(hipMemsetAsync(h->d_sum4, 0, 4 * sizeof(double), h->stream));
-    const unsigned grid = (unsigned)std::min<int64_t>((h->B + 255) / 256, 1024);
-    hipLaunchKernelGGL(summary_kernel, dim3(grid), dim3(256), 0, h->stream, h->d_report, h->B, h->d_sum4);
-    VP_HIP(hipGetLastError());
+    if (int rc = launch_summary(h, h->d_sum4)) return rc;
     if (rccl_comm) {
         vp_nccl_allreduce_t ar = resolve_nccl_allreduce();
         if (!ar) return fail(VP_ERR_UNSUPPORTED, "ncclAllReduce not found: link librccl or make librccl.so.1 loadable");
         const int rc = ar(h->d_sum4, h->d_sum4, 4, /*ncclDouble*/ 8, /*ncclSum*/ 0, rccl_comm, h->stream);
         if (rc != 0) return fail(VP_ERR_HIP, "ncclAllReduce failed with code " + std::to_string(rc));
     }
-    VP_HIP(hipMemcpyAsync(out, h->d_sum4, 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    VP_HIP(hipStreamSynchronize(h->stream));
-    return VP_ERR_OK;
+    return read_sum4(h, out);
 }
 
 int vp_set_fit_kernel(vp_batch *h, int which) {
