@@ -48,6 +48,9 @@ pub const VP_BASIS_EXP_DECAY: i32 = 1;
 pub const VP_BASIS_EXP_RATE: i32 = 2;
 pub const VP_BASIS_EXP_COS: i32 = 3;
 pub const VP_BASIS_SIN_PHASE: i32 = 4;
+pub const VP_BASIS_GAUSS: i32 = 6;
+pub const VP_BASIS_LORENTZ: i32 = 7;
+pub const VP_BASIS_LINEAR: i32 = 8;
 pub const VP_F64: i32 = 0;
 pub const VP_FLAG_OWN_STREAM: i32 = 8;
 pub const VP_FLAG_NO_GRID_RECURRENCE: i32 = 16;

@@ -66,10 +66,38 @@ enum {
                                shared_test_code/src/models.rs:310-372 (O'Leary example)                         */
     VP_BASIS_SIN_PHASE = 4, /* sin(p0*t+p1)            d/dp0 = t*cos(p0*t+p1) ; d/dp1 = cos(p0*t+p1)
                                src/test_helpers/mod.rs:28-52                                                     */
-    VP_BASIS_EXTERNAL = 5   /* evaluated by the CALLER: any SeparableNonlinearModel (src/model/mod.rs:239-363), in
+    VP_BASIS_EXTERNAL = 5,  /* evaluated by the CALLER: any SeparableNonlinearModel (src/model/mod.rs:239-363), in
                                particular the closure-based SeparableModel (:441-512).  Only produced by
                                vp_batch_create_external; see "models outside the descriptor language" below          */
+    /* peak and baseline kinds, d = t - p0 (see "device-column handles" below) */
+    VP_BASIS_GAUSS = 6,     /* exp(-d^2/(2 p1^2))      d/dp0 = f*d/p1^2 ; d/dp1 = f*d^2/p1^3                            */
+    VP_BASIS_LORENTZ = 7,   /* p1^2/(d^2 + p1^2)       d/dp0 = 2 p1^2 d/(d^2 + p1^2)^2 ; d/dp1 = 2 p1 d^2/(d^2 + p1^2)^2 */
+    VP_BASIS_LINEAR = 8     /* t                       invariant_function (no parameters): a sloped baseline            */
 };
+
+/*
+ * Device-column handles.  A descriptor that contains at least one of VP_BASIS_GAUSS / VP_BASIS_LORENTZ / VP_BASIS_LINEAR
+ * (next to any of the kinds 0..4) makes vp_batch_create build a DEVICE-COLUMN handle: one kernel (vp_cols.hpp) evaluates
+ * the unweighted columns Phi [B][n][m] and dPhi [B][p][m] of ALL its basis functions into two buffers the handle owns --
+ * B*n*m and B*p*m elements of the handle's dtype, allocated at the first call that needs them -- and the kernels of
+ * caller-evaluated models (below) do everything downstream, exactly as they do for a caller's columns.  A descriptor of
+ * the kinds 0..4 alone takes the in-register kernels as before.  On a device-column handle
+ *   vp_set_params, vp_evaluate, vp_basis, vp_residuals, vp_jacobian, vp_linear_coeffs, vp_cost, vp_params, vp_best_fit,
+ *   vp_statistics, vp_global_statistics, vp_weighted_data, vp_set_observations, vp_summary*, vp_reduce_cost work as on any
+ *   descriptor handle (shared and per-problem grids, weights, any S, both dtypes; m < n included);
+ *   vp_fit  runs the stepped LM of vp_fit_begin / _step_with_basis / _end inside the library: per step one launch of the
+ *           column kernel over the still-active problems (the step kernel's compacted list, read on the device) and one
+ *           step launch; the host looks at the active count every 8 steps.  Afterwards the handle's state is the fitted
+ *           point INCLUDING its columns: vp_residuals, vp_jacobian, vp_best_fit and the statistics need no further call.
+ *           m < n: VP_ERR_UNSUPPORTED (as for vp_fit_begin);
+ *   VP_ERR_UNSUPPORTED: vp_set_params_with_basis, vp_jacobian_with_derivatives, vp_evaluate_with_basis, vp_fit_begin,
+ *           vp_fit_step_with_basis, vp_fit_active_set, vp_fit_end (the handle is not caller-evaluated), vp_fit_trace,
+ *           vp_set_rhs_allreduce (as on caller-evaluated handles), vp_debug_gram_evaluate;
+ *   vp_set_fit_kernel, VP_FLAG_STREAM_ROWS and VP_FLAG_NO_GRID_RECURRENCE are accepted and have no effect.
+ * Parameters for which Phi is not finite (a NaN guess; p1 = 0 with p0 on a grid point: 0 / 0) are latched per problem in
+ * status[b], like a caller's non-finite columns; p1 = 0 elsewhere gives a finite Phi (exp(-inf) = 0) whose Gaussian
+ * derivatives are NaN -- a fit from there ends VP_TERM_NUMERICAL, as the reference's does.  The batch is never aborted.
+ */
 
 /*
  * Model descriptor == what SeparableModelBuilder::build() produces
@@ -266,7 +294,7 @@ int vp_basis(vp_batch *h, const void *alpha, void *Phi_out, void *dPhi_out, int 
  * The reference's plugin boundary is a TRAIT: any `SeparableNonlinearModel` (src/model/mod.rs:239-363) works with its
  * solver -- the closure-based `SeparableModel` (src/model/mod.rs:441-512, src/model/model_basis_function.rs:11-28) and
  * every hand-written impl (shared_test_code/src/models.rs:40-150).  A model the closed descriptor language above cannot
- * express (a Gaussian, a Lorentzian, a basis function of three parameters, a table look-up, ...) crosses this ABI as
+ * express (a pseudo-Voigt or any other basis function of three parameters, a table look-up, ...) crosses this ABI as
  * the VALUES the trait returns: the caller evaluates `eval()` -> Phi and `eval_partial_deriv(k)` -> its non-zero
  * columns; the device does everything downstream of them -- weighting (src/solvers/levmar/mod.rs:47,141), the
  * factorisation / truncated solve / residual (:51-59) and the Kaufman Jacobian (:101-201).

@@ -41,6 +41,13 @@ int vp_debug_lmpar_gram(int64_t B, int q, const double *Rj, const int32_t *ipvt,
  */
 int vp_debug_set_refit(vp_batch *h, int enabled);
 
+/*
+ * Measurement switches of a device-column handle (VP_BASIS_GAUSS / _LORENTZ / _LINEAR; tools/peak_kinds_probe.py):
+ * look_every >= 1: vp_fit reads the active count every look_every steps (default 8); results do not depend on it.
+ * nontemporal: stores of the column kernel, 1 (default) non-temporal, 0 ordinary; values do not depend on it.
+ */
+int vp_debug_set_column_fit(vp_batch *h, int look_every, int nontemporal);
+
 #ifdef __cplusplus
 }
 #endif

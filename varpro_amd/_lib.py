@@ -24,6 +24,8 @@ VP_FLAG_DEVICE_PTRS, VP_FLAG_T_PER_PROBLEM, VP_FLAG_W_PER_PROBLEM, VP_FLAG_OWN_S
 VP_FLAG_NO_GRID_RECURRENCE = 16
 VP_FLAG_STREAM_ROWS = 32
 VP_BASIS_SKIP_INVARIANT = 1
+VP_BASIS_CONST, VP_BASIS_EXP_DECAY, VP_BASIS_EXP_RATE, VP_BASIS_EXP_COS, VP_BASIS_SIN_PHASE, VP_BASIS_EXTERNAL = 0, 1, 2, 3, 4, 5
+VP_BASIS_GAUSS, VP_BASIS_LORENTZ, VP_BASIS_LINEAR = 6, 7, 8
 VP_FIT_DERIVATIVES_ON_ACCEPT = 1
 VP_WANT_BASIS, VP_WANT_DERIVATIVES = 1, 2
 VP_KERNEL_EVALUATE, VP_KERNEL_BASIS, VP_KERNEL_FIT = 0, 1, 2
@@ -53,7 +55,7 @@ ABI_SYMBOLS = [
 
 
 # test hooks (include/varpro_hip_debug.h): exported by the library, not part of the drop-in boundary
-DEBUG_SYMBOLS = ["vp_debug_gram_evaluate", "vp_debug_lmpar_gram", "vp_debug_set_refit"]
+DEBUG_SYMBOLS = ["vp_debug_gram_evaluate", "vp_debug_lmpar_gram", "vp_debug_set_refit", "vp_debug_set_column_fit"]
 
 
 class VarproHipUnavailable(ImportError):
@@ -139,6 +141,8 @@ def load():
     lib.vp_debug_gram_evaluate.argtypes = [vp, vp, vp]
     lib.vp_debug_lmpar_gram.argtypes = [C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     lib.vp_debug_set_refit.argtypes = [vp, C.c_int]
+    if hasattr(lib, "vp_debug_set_column_fit"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no such hook)
+        lib.vp_debug_set_column_fit.argtypes = [vp, C.c_int, C.c_int]
     lib.vp_statistics.argtypes = [vp, vp, vp, vp, vp]
     lib.vp_global_statistics.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.vp_summary.argtypes = [vp, dp]

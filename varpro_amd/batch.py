@@ -649,6 +649,11 @@ class BatchProblem:
         instead of re-fitting it with scaled columns in vp_fit's second launch"""
         check(self.lib.vp_debug_set_refit(self._h, int(enable)))
 
+    def set_column_fit(self, look_every=8, nontemporal=1):
+        """measurement switches of a handle whose model has a peak / baseline kind (include/varpro_hip_debug.h:
+        vp_debug_set_column_fit): the step interval at which ``fit`` reads the active count, and the column kernel's store mode"""
+        check(self.lib.vp_debug_set_column_fit(self._h, int(look_every), int(nontemporal)))
+
     def set_timing(self, enable=True):
         check(self.lib.vp_set_timing(self._h, int(enable)))
 

@@ -36,11 +36,15 @@ enum class Basis : int32_t {
     ExpDecay = VP_BASIS_EXP_DECAY,
     ExpRate = VP_BASIS_EXP_RATE,
     ExpCos = VP_BASIS_EXP_COS,
-    SinPhase = VP_BASIS_SIN_PHASE
+    SinPhase = VP_BASIS_SIN_PHASE,
+    Gauss = VP_BASIS_GAUSS,     // peak kinds: the device evaluates their columns into memory (device-column handles)
+    Lorentz = VP_BASIS_LORENTZ,
+    Linear = VP_BASIS_LINEAR
 };
 inline int arity(Basis k) {
     switch (k) {
-    case Basis::Const: return 0;
+    case Basis::Const:
+    case Basis::Linear: return 0;
     case Basis::ExpDecay:
     case Basis::ExpRate: return 1;
     default: return 2;

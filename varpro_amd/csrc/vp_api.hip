@@ -18,6 +18,7 @@
 #include "vp_extfit_api.hpp"
 #include "vp_mrhs.hpp"
 #include "vp_gstats.hpp"
+#include "vp_cols.hpp"
 
 using namespace vp;
 
@@ -310,6 +311,14 @@ struct __attribute__((visibility("hidden"))) vp_batch {
     int32_t ext_pb[VP_MAX_PAIRS] = {}, ext_pp[VP_MAX_PAIRS] = {};
     const void *ext_phi = nullptr, *ext_dphi = nullptr;
     void *ext_phi_own = nullptr, *ext_dphi_own = nullptr;
+    // device-column handle (a descriptor with VP_BASIS_GAUSS / _LORENTZ / _LINEAR): `external` is set as well -- everything
+    // downstream of the columns is the caller-evaluated path -- and the columns come from the column kernel (vp_cols.hpp),
+    // which evaluates col_model on the handle's grid into the two owned buffers
+    bool devcols = false;
+    vp_model_desc col_model = {};
+    void *col_phi = nullptr, *col_dphi = nullptr; // [B][n][rows], [B][p][rows]; allocated at first use
+    int col_look = 8;    // vp_fit: the host reads the active count every col_look steps (vp_debug_set_column_fit; measured)
+    int col_nt = 1;      // stores of the column kernel: 1 = non-temporal, 0 = ordinary (vp_debug_set_column_fit; measured)
     // batched reverse-communication LM fit of a caller-evaluated model (vp_fit_begin / vp_fit_step_with_basis / vp_fit_end)
     void *d_xf_state = nullptr;      // [B] LM records of the step kernel
     void *d_xf_trial = nullptr;      // [B][q] trial points of the last step
@@ -590,6 +599,42 @@ int alloc_gen_ws(vp_batch *h, int64_t work_items) {
 int ensure_gen_ws(vp_batch *h) { return h->kern->uses_gen_ws ? alloc_gen_ws(h, h->B * h->S) : 0; }
 
 int ensure_R(vp_batch *h) { return h->ensure(h->d_R, (size_t)h->B * h->S * h->m * tsize(h->dtype)); }
+
+// ---- device-column handles: the column kernel (vp_cols.hpp) ------------------------------------------------------------
+// rows of a column: the caller's m (a handle padded for m < n keeps the caller's rows in its columns, like ext_rows)
+int64_t col_rows(const vp_batch *h) { return h->m_user ? h->m_user : h->m; }
+// the launch record of the handle's model on the handle's grid; outputs and the problem selection are the caller's
+void fill_cols_params(const vp_batch *h, ColsParams &c) {
+    std::memset(&c, 0, sizeof(c));
+    c.dtype = h->dtype;
+    c.model = h->col_model;
+    c.t = h->d_t;
+    c.t_stride = (h->flags & VP_FLAG_T_PER_PROBLEM) ? h->m : 0;
+    c.m = (int)col_rows(h);
+    c.B = h->B;
+    c.stream = h->stream;
+}
+// Phi and dPhi of `alpha_dev` [B][q] into the handle's own buffers, which become the columns of the caller-evaluated path.
+// list / count (device): only these problems, `bound` an upper bound of *count; null: all B
+int fill_own_columns(vp_batch *h, const void *alpha_dev, const int32_t *list, const int32_t *count, int64_t bound) {
+    const size_t ts = tsize(h->dtype), rows = (size_t)col_rows(h);
+    if (int rc = h->ensure(h->col_phi, (size_t)h->B * h->n * rows * ts)) return rc;
+    if (h->ext_np > 0)
+        if (int rc = h->ensure(h->col_dphi, (size_t)h->B * h->ext_np * rows * ts)) return rc;
+    ColsParams c;
+    fill_cols_params(h, c);
+    c.alpha = alpha_dev;
+    c.phi = h->col_phi;
+    c.dphi = h->col_dphi;
+    c.list = list;
+    c.count = count;
+    c.nt = h->col_nt == 1 ? 1 : 0;
+    if (list) c.B = bound;
+    if (int rc = cols_fill(c)) return fail(rc, "column kernel launch failed");
+    h->ext_phi = h->col_phi;
+    h->ext_dphi = h->col_dphi;
+    return 0;
+}
 
 // ---- the steps several entry points share ---------------------------------------------------------------------------
 // the caller's parameters (device or host array, by the handle's flags) -> d_alpha
@@ -1286,6 +1331,35 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
     if (ext) npairs = ext->np; // caller-evaluated model: shape and pair table only, nothing to classify
     else if (classify_model(*model, fa, fb, fc, npairs) < 0) return fail(VP_ERR_INVALID, "malformed model descriptor");
     if (npairs > VP_MAX_PAIRS) return fail(VP_ERR_INVALID, "too many dependency pairs");
+    // a descriptor with a peak / baseline kind: a device-column handle -- the state vp_batch_create_external builds (shape +
+    // the descriptor's pairs in model order) plus the grid and the descriptor for the column kernel
+    bool devcols = false;
+    if (!ext)
+        for (int j = 0; j < model->n_basis; ++j)
+            if (model->kind[j] == VP_BASIS_GAUSS || model->kind[j] == VP_BASIS_LORENTZ || model->kind[j] == VP_BASIS_LINEAR)
+                devcols = true;
+    vp_model_desc shape_desc;
+    int32_t dc_pb[VP_MAX_PAIRS], dc_pp[VP_MAX_PAIRS];
+    ExtSpec dc_ext{0, dc_pb, dc_pp};
+    const vp_model_desc *const descriptor = model;
+    if (devcols) {
+        for (int j = 0; j < model->n_basis; ++j)
+            for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k)
+                if (model->param[j][k] >= 0) {
+                    dc_pb[dc_ext.np] = j;
+                    dc_pp[dc_ext.np] = model->param[j][k];
+                    ++dc_ext.np;
+                }
+        std::memset(&shape_desc, 0, sizeof(shape_desc)); // (as vp_batch_create_external describes a caller-evaluated model)
+        shape_desc.n_basis = model->n_basis;
+        shape_desc.n_params = model->n_params;
+        for (int j = 0; j < VP_MAX_BASIS; ++j) {
+            shape_desc.kind[j] = j < model->n_basis ? VP_BASIS_EXTERNAL : 0;
+            for (int a = 0; a < VP_MAX_BASIS_PARAMS; ++a) shape_desc.param[j][a] = -1;
+        }
+        model = &shape_desc;
+        ext = &dc_ext;
+    }
 
     int ndev = vp_device_count();
     if (ndev <= 0) return fail(VP_ERR_NO_DEVICE, "no HIP device visible");
@@ -1333,6 +1407,10 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
             h->ext_pp[i] = ext->pp[i];
         }
     }
+    if (devcols) {
+        h->devcols = true;
+        h->col_model = *descriptor;
+    }
     if (int rc = batch_init(h, t, Y, w, hip_stream, data_on_device)) {
         vp_batch_destroy(h);
         return rc;
@@ -1358,9 +1436,15 @@ void vp_batch_destroy(vp_batch *h) {
 
 // ---- caller-evaluated models (vp_batch_create_external) -----------------------------------------------------------
 #define VP_NOT_EXTERNAL(h, what)                                                                                       \
-    if ((h)->external)                                                                                                 \
+    if ((h)->external && !(h)->devcols)                                                                                \
     return fail(VP_ERR_UNSUPPORTED, what ": the handle's model is evaluated by the caller (vp_set_params_with_basis / "   \
                                          "vp_evaluate_with_basis)")
+// ... and the entries of caller-evaluated handles on a device-column handle
+#define VP_NOT_DEVCOLS(h, what)                                                                                        \
+    if ((h)->devcols)                                                                                                  \
+    return fail(VP_ERR_UNSUPPORTED, what ": the handle's model is a descriptor the device evaluates (vp_set_params / "    \
+                                         "vp_evaluate / vp_fit); only handles made by vp_batch_create_external take the "  \
+                                         "caller's columns")
 
 // where the kernels find the columns of the current parameters: the caller's device arrays, or staged copies of host arrays
 static int ext_stage(vp_batch *h, const void *user, int64_t cols, const void *&dev, void *&own) {
@@ -1407,6 +1491,7 @@ static int cache_at_alpha(vp_batch *h) {
 
 int vp_set_params_with_basis(vp_batch *h, const void *alpha, const void *Phi, const void *dPhi) {
     VP_ENTER(h);
+    VP_NOT_DEVCOLS(h, "vp_set_params_with_basis");
     if (!h->external) return fail(VP_ERR_UNSUPPORTED, "vp_set_params_with_basis needs a handle made by vp_batch_create_external");
     if (!alpha || !Phi) return fail(VP_ERR_INVALID, "null alpha / Phi");
     if (int rc = upload_alpha(h, alpha)) return rc;
@@ -1417,6 +1502,7 @@ int vp_set_params_with_basis(vp_batch *h, const void *alpha, const void *Phi, co
 
 int vp_jacobian_with_derivatives(vp_batch *h, const void *dPhi, void *J_out, int32_t *status) {
     VP_ENTER(h);
+    VP_NOT_DEVCOLS(h, "vp_jacobian_with_derivatives");
     if (!h->external) return fail(VP_ERR_UNSUPPORTED, "vp_jacobian_with_derivatives needs a handle made by vp_batch_create_external");
     if (!h->have_params) return copy_status(h, status) ? VP_ERR_HIP : VP_ERR_OK; // jacobian() before set_params(): None
     if (!dPhi && h->ext_np > 0) return fail(VP_ERR_INVALID, "null dPhi");
@@ -1427,6 +1513,7 @@ int vp_jacobian_with_derivatives(vp_batch *h, const void *dPhi, void *J_out, int
 int vp_evaluate_with_basis(vp_batch *h, const void *alpha, const void *Phi, const void *dPhi, void *r_out, void *J_out,
                            void *C_out, double *cost_out, int32_t *status) {
     VP_ENTER(h);
+    VP_NOT_DEVCOLS(h, "vp_evaluate_with_basis");
     if (!h->external) return fail(VP_ERR_UNSUPPORTED, "vp_evaluate_with_basis needs a handle made by vp_batch_create_external");
     if (!alpha || !Phi) return fail(VP_ERR_INVALID, "null alpha / Phi");
     if (J_out && !dPhi && h->ext_np > 0) return fail(VP_ERR_INVALID, "a Jacobian needs the derivative columns dPhi");
@@ -1440,14 +1527,25 @@ int vp_evaluate_with_basis(vp_batch *h, const void *alpha, const void *Phi, cons
 
 // ---- batched LM fit of a caller-evaluated model by reverse communication (vp_extfit.hpp) --------------------------
 // == LevMarSolver::fit (src/solvers/levmar/mod.rs:238-254) over the trait surface (src/model/mod.rs:239-363)
+static int xf_begin(vp_batch *h, const vp_lm_opts *opts, const void *alpha0, int flags);
+
 int vp_fit_begin(vp_batch *h, const vp_lm_opts *opts, const void *alpha0, int flags) {
     VP_ENTER(h);
+    VP_NOT_DEVCOLS(h, "vp_fit_begin");
     if (!h->external)
         return fail(VP_ERR_UNSUPPORTED, "vp_fit_begin needs a handle made by vp_batch_create_external (descriptor models: vp_fit)");
+    return xf_begin(h, opts, alpha0, flags);
+}
+
+// (also the start of a device-column handle's vp_fit)
+static int xf_begin(vp_batch *h, const vp_lm_opts *opts, const void *alpha0, int flags) {
     if (!alpha0) return fail(VP_ERR_INVALID, "null alpha0");
     if (flags & ~VP_FIT_DERIVATIVES_ON_ACCEPT) return fail(VP_ERR_INVALID, "unknown vp_fit_begin flag");
     if (h->q <= 0) return fail(VP_ERR_INVALID, "a fit needs at least one nonlinear parameter");
-    if (h->m_user) return fail(VP_ERR_UNSUPPORTED, "the batched fit of caller-evaluated models needs m >= n");
+    if (h->m_user)
+        return fail(VP_ERR_UNSUPPORTED, h->devcols ? "vp_fit of a model with VP_BASIS_GAUSS / _LORENTZ / _LINEAR needs m >= n (fewer "
+                                                     "samples than basis functions: vp_evaluate and the trait-level calls work)"
+                                                   : "the batched fit of caller-evaluated models needs m >= n");
     const size_t rec = external_fit_rec_bytes(h->dtype, h->n, h->ext_np, h->q, h->m);
     if (!rec) return fail(VP_ERR_UNSUPPORTED, "no LM step kernel for this number of parameters");
     const size_t ts = tsize(h->dtype);
@@ -1488,6 +1586,7 @@ int vp_fit_begin(vp_batch *h, const vp_lm_opts *opts, const void *alpha0, int fl
 int vp_fit_step_with_basis(vp_batch *h, const void *Phi, const void *dPhi, void *alpha_trial_out, int32_t *want_out,
                            int64_t *n_active_out) {
     VP_ENTER(h);
+    VP_NOT_DEVCOLS(h, "vp_fit_step_with_basis");
     if (!h->external || !h->xf_running) return fail(VP_ERR_INVALID, "vp_fit_step_with_basis without vp_fit_begin");
     if (!Phi) return fail(VP_ERR_INVALID, "null Phi");
     const bool lazy = (h->xf_flags & VP_FIT_DERIVATIVES_ON_ACCEPT) != 0;
@@ -1526,6 +1625,7 @@ int vp_fit_step_with_basis(vp_batch *h, const void *Phi, const void *dPhi, void 
 
 int vp_fit_active_set(vp_batch *h, int32_t *index_out, int32_t *count_out) {
     VP_ENTER(h);
+    VP_NOT_DEVCOLS(h, "vp_fit_active_set");
     if (!h->external || !h->xf_running) return fail(VP_ERR_INVALID, "vp_fit_active_set without vp_fit_begin");
     if (h->xf_init) return fail(VP_ERR_INVALID, "vp_fit_active_set before the first vp_fit_step_with_basis");
     const int slot = (int)((h->xf_steps - 1) & 1); // the list and the counter the last step's LM kernel wrote
@@ -1536,6 +1636,7 @@ int vp_fit_active_set(vp_batch *h, int32_t *index_out, int32_t *count_out) {
 
 int vp_fit_end(vp_batch *h, void *alpha_out, void *C_out, vp_report *rep) {
     VP_ENTER(h);
+    VP_NOT_DEVCOLS(h, "vp_fit_end");
     if (!h->external || !h->xf_running) return fail(VP_ERR_INVALID, "vp_fit_end without vp_fit_begin");
     if (h->xf_init) return fail(VP_ERR_INVALID, "vp_fit_end before the first vp_fit_step_with_basis");
     h->xf_running = false;
@@ -1551,6 +1652,8 @@ int vp_set_params(vp_batch *h, const void *alpha) {
     VP_NOT_EXTERNAL(h, "vp_set_params");
     if (!alpha) return fail(VP_ERR_INVALID, "null alpha");
     if (int rc = upload_alpha(h, alpha)) return rc;
+    if (h->devcols)
+        if (int rc = fill_own_columns(h, h->d_alpha, nullptr, nullptr, h->B)) return rc;
     return cache_at_alpha(h);
 }
 
@@ -1652,6 +1755,12 @@ int vp_evaluate(vp_batch *h, const void *alpha, void *r_out, void *J_out, void *
     VP_NOT_EXTERNAL(h, "vp_evaluate");
     if (!alpha) return fail(VP_ERR_INVALID, "null alpha");
     if (int rc = upload_alpha(h, alpha)) return rc;
+    if (h->devcols) {
+        if (int rc = fill_own_columns(h, h->d_alpha, nullptr, nullptr, h->B)) return rc;
+        if (int rc = evaluate_at_alpha(h, r_out, J_out, C_out, cost_out, status)) return rc;
+        if (!device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream));
+        return VP_ERR_OK;
+    }
     return evaluate_at_alpha(h, r_out, J_out, C_out, cost_out, status);
 }
 
@@ -1660,6 +1769,32 @@ int vp_basis(vp_batch *h, const void *alpha, void *Phi_out, void *dPhi_out, int 
     VP_NOT_EXTERNAL(h, "vp_basis");
     if (!alpha) return fail(VP_ERR_INVALID, "null alpha");
     const size_t ts = tsize(h->dtype);
+    if (h->devcols) { // the column kernel straight into the caller's arrays (host-pointer handles: staged)
+        int nc = 0;
+        for (int j = 0; j < h->n; ++j)
+            if (!((flags & VP_BASIS_SKIP_INVARIANT) && h->col_model.kind[j] == VP_BASIS_CONST)) ++nc;
+        const size_t rows = (size_t)col_rows(h);
+        InBuf a;
+        if (int rc = a.init(h, alpha, (size_t)h->B * h->q * ts)) return rc;
+        OutBuf phi, dphi;
+        if (int rc = phi.init(h, Phi_out, (size_t)h->B * nc * rows * ts)) return rc;
+        if (int rc = dphi.init(h, dPhi_out, (size_t)h->B * h->ext_np * rows * ts)) return rc;
+        ColsParams c;
+        fill_cols_params(h, c);
+        c.alpha = a.dptr;
+        c.phi = phi.dptr;
+        c.dphi = dphi.dptr;
+        c.skip_invariant = (flags & VP_BASIS_SKIP_INVARIANT) ? 1 : 0;
+        c.nt = h->col_nt == 0 ? 0 : 1;
+        Timer tm(h, VP_KERNEL_BASIS);
+        const int rc = cols_fill(c);
+        tm.stop();
+        if (rc != VP_ERR_OK) return fail(rc, "column kernel launch failed");
+        if (int rc2 = phi.finish(h)) return rc2;
+        if (int rc2 = dphi.finish(h)) return rc2;
+        if (!device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream));
+        return VP_ERR_OK;
+    }
     int ncols = 0;
     for (int j = 0; j < h->n; ++j)
         if (!((flags & VP_BASIS_SKIP_INVARIANT) && h->model.kind[j] == VP_BASIS_CONST)) ++ncols;
@@ -1684,7 +1819,69 @@ int vp_basis(vp_batch *h, const void *alpha, void *Phi_out, void *dPhi_out, int 
     return VP_ERR_OK;
 }
 
+// vp_fit of a device-column handle: the stepped LM of caller-evaluated models (xf_begin / xf_step / vp_fit_end's state)
+// with the column kernel in the caller's place.  Per step: the columns of the still-active problems at their trial points
+// (the list and the count the previous step's LM kernel left on the device), then the step.  The host reads the active
+// count every col_look steps (8 unless vp_debug_set_column_fit says otherwise) -- a synchronisation; the steps in between are enqueued blind, and a step past the end
+// of every fit is two empty launches.  Every problem ends within patience*(q+1) evaluations, so the loop does.
+namespace {
+// one step of that loop: the LM step on the handle's own columns, the trial points stay on the device; `look`: read the
+// active count (synchronises the stream)
+int devcols_step(vp_batch *h, const bool look, int64_t &n_active) {
+    ExtFitParams p;
+    fill_ext_params(h, p);
+    p.alpha_trial = h->d_xf_trial;
+    p.want = h->d_xf_want;
+    if (int rc = external_fit_step(p)) return fail(rc, "fit step kernel launch failed");
+    h->xf_init = false;
+    h->xf_steps += 1;
+    if (look) {
+        VP_HIP(hipMemcpyAsync(h->h_xf_nactive, h->d_xf_nactive + ((h->xf_steps - 1) & 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        VP_HIP(hipStreamSynchronize(h->stream));
+        n_active = h->xf_known_active = *h->h_xf_nactive;
+    }
+    return VP_ERR_OK;
+}
+int devcols_fit(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C_out, vp_report *rep) {
+    if (!alpha_inout) return fail(VP_ERR_INVALID, "null alpha");
+    if (int rc = xf_begin(h, opts, alpha_inout, 0)) return rc;
+    const int64_t limit = 2 * ((int64_t)h->xf_opts.patience * (h->q + 1) + 2);
+    Timer tm(h, VP_KERNEL_FIT);
+    for (int64_t step = 1; step <= limit; ++step) {
+        int rc;
+        if (h->xf_init) {
+            rc = fill_own_columns(h, h->d_alpha, nullptr, nullptr, h->B);
+        } else {
+            const int slot = (int)((h->xf_steps + 1) & 1); // what the previous step's LM kernel wrote
+            const int64_t bound = h->xf_known_active < h->B ? std::max<int64_t>(h->xf_known_active, 1) : h->B;
+            rc = fill_own_columns(h, h->d_xf_trial, h->d_xf_active + (size_t)slot * h->B, h->d_xf_nactive + slot, bound);
+        }
+        if (rc) {
+            h->xf_running = false;
+            return rc;
+        }
+        const bool look = step % h->col_look == 0 || step == limit;
+        int64_t nact = -1;
+        if (int rc2 = devcols_step(h, look, nact)) {
+            h->xf_running = false;
+            return rc2;
+        }
+        if (look && nact == 0) break;
+    }
+    h->xf_running = false;
+    after_fit(h);
+    // the handle's state is the fitted point, its columns included
+    if (int rc = fill_own_columns(h, h->d_alpha, nullptr, nullptr, h->B)) return rc;
+    tm.stop();
+    return copy_fit_out(h, alpha_inout, C_out, rep);
+}
+} // namespace
+
 int vp_fit(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C_out, vp_report *rep) {
+    if (h && h->devcols) {
+        VP_ENTER(h);
+        return devcols_fit(h, opts, alpha_inout, C_out, rep);
+    }
     return vp_fit_trace(h, opts, alpha_inout, C_out, rep, nullptr, 0);
 }
 
@@ -1736,6 +1933,9 @@ int rescue_refit(vp_batch *h, const LaunchParams &fit_params) {
 int vp_fit_trace(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C_out, vp_report *rep,
                  double *trace_out, int trace_rows) {
     VP_ENTER(h);
+    if (h->devcols)
+        return fail(VP_ERR_UNSUPPORTED, "vp_fit_trace: a device-column handle (VP_BASIS_GAUSS / _LORENTZ / _LINEAR) fits by the "
+                                        "stepped LM of caller-evaluated models, which records no trace");
     VP_NOT_EXTERNAL(h, "vp_fit");
     if (!alpha_inout) return fail(VP_ERR_INVALID, "null alpha");
     if (h->m_user && (int64_t)h->q > h->m_user * h->S) {
@@ -1783,6 +1983,15 @@ int vp_fit_trace(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C
     after_fit(h);
     if (int rc2 = copy_fit_out(h, alpha_inout, C_out, rep)) return rc2;
     return tr.finish(h);
+}
+
+int vp_debug_set_column_fit(vp_batch *h, int look_every, int nontemporal) {
+    VP_ENTER(h);
+    if (!h->devcols) return fail(VP_ERR_UNSUPPORTED, "vp_debug_set_column_fit needs a device-column handle");
+    if (look_every < 1 || nontemporal < 0 || nontemporal > 1) return fail(VP_ERR_INVALID, "vp_debug_set_column_fit: bad argument");
+    h->col_look = look_every;
+    h->col_nt = nontemporal;
+    return VP_ERR_OK;
 }
 
 int vp_debug_set_refit(vp_batch *h, int enabled) {
@@ -1879,6 +2088,9 @@ int vp_debug_lmpar_gram(int64_t B, int q, const double *Rj, const int32_t *ipvt,
 
 int vp_set_rhs_allreduce(vp_batch *h, vp_allreduce_fn fn, void *user, int64_t global_rhs_count) {
     VP_ENTER(h);
+    if (fn && h->devcols)
+        return fail(VP_ERR_UNSUPPORTED, "right-hand-side sharding is not available on a device-column handle (VP_BASIS_GAUSS / "
+                                        "_LORENTZ / _LINEAR), as on caller-evaluated handles");
     if (fn) {
         if (h->S <= 1 || (!h->have_mrhs && !h->kern->mrhs_fit_whole))
             return fail(VP_ERR_UNSUPPORTED, "right-hand-side sharding needs a handle with S > 1");
@@ -2160,6 +2372,9 @@ static int kind_arity(int kind) {
     case VP_BASIS_EXP_RATE: return 1;
     case VP_BASIS_EXP_COS:
     case VP_BASIS_SIN_PHASE: return 2;
+    case VP_BASIS_GAUSS:
+    case VP_BASIS_LORENTZ: return 2;
+    case VP_BASIS_LINEAR: return 0;
     default: return -1; // (VP_BASIS_EXTERNAL never reaches a descriptor: vp_batch_create_external only)
     }
 }

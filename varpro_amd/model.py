@@ -24,8 +24,43 @@ class basis:
     EXP_RATE = 2    # exp(-p0 t)
     EXP_COS = 3     # exp(-p0 t) cos(p1 t)  shared_test_code/src/models.rs:310-372
     SIN_PHASE = 4   # sin(p0 t + p1)        src/test_helpers/mod.rs:28-52
-    ARITY = {CONST: 0, EXP_DECAY: 1, EXP_RATE: 1, EXP_COS: 2, SIN_PHASE: 2}
-    NAME = {CONST: "const", EXP_DECAY: "exp_decay", EXP_RATE: "exp_rate", EXP_COS: "exp_cos", SIN_PHASE: "sin_phase"}
+    # (5 == VP_BASIS_EXTERNAL: a model the caller evaluates, ExternalModel below)
+    GAUSS = 6       # exp(-(t - p0)^2 / (2 p1^2))     peak at p0, standard deviation p1
+    LORENTZ = 7     # p1^2 / ((t - p0)^2 + p1^2)      peak at p0, half width at half maximum p1
+    LINEAR = 8      # t                     (invariant_function: a sloped baseline)
+    ARITY = {CONST: 0, EXP_DECAY: 1, EXP_RATE: 1, EXP_COS: 2, SIN_PHASE: 2, GAUSS: 2, LORENTZ: 2, LINEAR: 0}
+    NAME = {CONST: "const", EXP_DECAY: "exp_decay", EXP_RATE: "exp_rate", EXP_COS: "exp_cos", SIN_PHASE: "sin_phase",
+            GAUSS: "gauss", LORENTZ: "lorentz", LINEAR: "linear"}
+    # kinds whose columns the device evaluates into memory (a device-column handle, include/varpro_hip.h)
+    DEVICE_COLUMN = (GAUSS, LORENTZ, LINEAR)
+
+
+def _kind_columns(kind, x, p0, p1):
+    """numpy mirror of one basis kind: (f, [df/dp0, df/dp1][:arity]) on the grid x (include/varpro_hip.h)"""
+    if kind == basis.CONST:
+        return np.ones_like(x), []
+    if kind == basis.LINEAR:
+        return x.copy(), []
+    if kind == basis.EXP_DECAY:
+        f = np.exp(-x / p0)
+        return f, [f * x / p0 ** 2]
+    if kind == basis.EXP_RATE:
+        f = np.exp(-p0 * x)
+        return f, [-x * f]
+    if kind == basis.EXP_COS:
+        e = np.exp(-p0 * x)
+        f = e * np.cos(p1 * x)
+        return f, [-x * f, -x * e * np.sin(p1 * x)]
+    if kind == basis.SIN_PHASE:
+        c = np.cos(p0 * x + p1)
+        return np.sin(p0 * x + p1), [x * c, c]
+    if kind == basis.GAUSS:
+        f = np.exp(-0.5 * ((x - p0) / p1) ** 2)
+        return f, [f * (x - p0) / p1 ** 2, f * (x - p0) ** 2 / p1 ** 3]
+    if kind == basis.LORENTZ:
+        den = (x - p0) ** 2 + p1 ** 2
+        return p1 ** 2 / den, [2 * p1 ** 2 * (x - p0) / den ** 2, 2 * p1 * (x - p0) ** 2 / den ** 2]
+    raise ModelError("unknown basis kind %r" % (kind,))
 
 
 class ModelBuildError(ValueError):
@@ -94,7 +129,27 @@ class SeparableModel:
                 d.param[j][a] = pi
         return d
 
+    def _basis_host(self):
+        """Phi (1, n, m), dPhi (1, p, m) in numpy: the host mirror of the column kernel (vp_cols.hpp)"""
+        x = self.x
+        a = self._alpha
+        phi = np.empty((1, len(self.kinds), x.size), dtype=self.dtype)
+        dphi = np.empty((1, len(self.pairs), x.size), dtype=self.dtype)
+        pair = 0
+        with np.errstate(all="ignore"):
+            for j, (kind, ps) in enumerate(zip(self.kinds, self.param_indices)):
+                args = [a[pi] for pi in ps] + [None, None]
+                f, ds = _kind_columns(kind, x, args[0], args[1])
+                phi[0, j] = f
+                for d in ds:
+                    dphi[0, pair] = d
+                    pair += 1
+        return phi, dphi
+
     def _basis(self):
+        # peak / baseline kinds: the model surface is evaluated on the host (the device evaluates them for BatchProblem)
+        if any(k in basis.DEVICE_COLUMN for k in self.kinds):
+            return self._basis_host()
         from .batch import BatchProblem
         # a data-free handle is enough for the Phi kernel; y is a dummy column
         bp = BatchProblem(self, np.zeros((1, self.x.size), dtype=self.dtype), x=self.x)
