@@ -54,6 +54,8 @@ pub const VP_BASIS_LINEAR: i32 = 8;
 pub const VP_F64: i32 = 0;
 pub const VP_FLAG_OWN_STREAM: i32 = 8;
 pub const VP_FLAG_NO_GRID_RECURRENCE: i32 = 16;
+/// a descriptor of the kinds 0..4 alone becomes a device-column handle (it then takes `vp_set_bounds`)
+pub const VP_FLAG_DEVICE_COLUMNS: i32 = 64;
 
 #[link(name = "varpro_hip")]
 extern "C" {
@@ -68,6 +70,8 @@ extern "C" {
     pub fn vp_linear_coeffs(h: *mut vp_batch, c_out: *mut c_void, status: *mut i32) -> i32;
     pub fn vp_weighted_data(h: *mut vp_batch, yw_out: *mut c_void) -> i32;
     pub fn vp_set_observations(h: *mut vp_batch, y: *const c_void) -> i32;
+    /// box bounds of `vp_fit` on a device-column handle: host doubles `[q]` or `[B][q]`, infinite = unbounded, both null clears
+    pub fn vp_set_bounds(h: *mut vp_batch, lower: *const f64, upper: *const f64, per_problem: i32) -> i32;
     pub fn vp_cost(h: *mut vp_batch, cost_out: *mut f64) -> i32;
     pub fn vp_evaluate(h: *mut vp_batch, alpha: *const c_void, r: *mut c_void, j: *mut c_void, c: *mut c_void,
         cost: *mut f64, status: *mut i32) -> i32;

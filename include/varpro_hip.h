@@ -81,7 +81,9 @@ enum {
  * the unweighted columns Phi [B][n][m] and dPhi [B][p][m] of ALL its basis functions into two buffers the handle owns --
  * B*n*m and B*p*m elements of the handle's dtype, allocated at the first call that needs them -- and the kernels of
  * caller-evaluated models (below) do everything downstream, exactly as they do for a caller's columns.  A descriptor of
- * the kinds 0..4 alone takes the in-register kernels as before.  On a device-column handle
+ * the kinds 0..4 alone takes the in-register kernels as before -- unless the handle is created with
+ * VP_FLAG_DEVICE_COLUMNS, which makes a device-column handle of any descriptor (the column kernel evaluates all eight
+ * kinds), e.g. to bound the decay times of a multi-exponential fit.  On a device-column handle
  *   vp_set_params, vp_evaluate, vp_basis, vp_residuals, vp_jacobian, vp_linear_coeffs, vp_cost, vp_params, vp_best_fit,
  *   vp_statistics, vp_global_statistics, vp_weighted_data, vp_set_observations, vp_summary*, vp_reduce_cost work as on any
  *   descriptor handle (shared and per-problem grids, weights, any S, both dtypes; m < n included);
@@ -93,7 +95,23 @@ enum {
  *   VP_ERR_UNSUPPORTED: vp_set_params_with_basis, vp_jacobian_with_derivatives, vp_evaluate_with_basis, vp_fit_begin,
  *           vp_fit_step_with_basis, vp_fit_active_set, vp_fit_end (the handle is not caller-evaluated), vp_fit_trace,
  *           vp_set_rhs_allreduce (as on caller-evaluated handles), vp_debug_gram_evaluate;
- *   vp_set_fit_kernel, VP_FLAG_STREAM_ROWS and VP_FLAG_NO_GRID_RECURRENCE are accepted and have no effect.
+ *   vp_set_fit_kernel, VP_FLAG_STREAM_ROWS and VP_FLAG_NO_GRID_RECURRENCE are accepted and have no effect;
+ *   vp_set_bounds  puts box bounds on the nonlinear parameters of vp_fit (only device-column handles take them).  A bounded
+ *           fit is a smooth re-parameterisation alpha = g(u) in the manner of MINUIT / lmfit -- per parameter
+ *               lo and hi:  alpha = lo + (hi - lo)/2 (sin u + 1)      lo only:  alpha = lo - 1 + sqrt(u^2 + 1)
+ *               hi only:    alpha = hi + 1 - sqrt(u^2 + 1)            neither:  alpha = u
+ *           -- and the unchanged LM drivers iterate on u: vp_fit maps alpha0 to u (a guess outside the box is clamped
+ *           onto it first), a bounded variant of the column kernel evaluates the model at g(u) and scales the derivative
+ *           columns by dalpha/du, and the result is mapped back.  Every returned parameter lies inside its box, bounds
+ *           included, exactly (the value is clamped after g; fp32 handles round the box inwards).  The returned alpha is,
+ *           bit for bit, the point at which the handle's final columns were evaluated, so vp_params, vp_residuals,
+ *           vp_jacobian, vp_best_fit, vp_statistics and vp_global_statistics are in the caller's parameters and need no
+ *           further call, as after any fit.  To know:
+ *             - ftol / xtol / gtol act on u, as in lmfit;
+ *             - a start ON a bound stays on it (dalpha/du = 0 there): start strictly inside the box;
+ *             - the statistics of a parameter that ends on a bound are those of the unconstrained linearisation at that
+ *               point (they do not know about the bound);
+ *             - bounds constrain vp_fit only: vp_set_params, vp_evaluate and vp_basis take alpha as given, unclipped.
  * Parameters for which Phi is not finite (a NaN guess; p1 = 0 with p0 on a grid point: 0 / 0) are latched per problem in
  * status[b], like a caller's non-finite columns; p1 = 0 elsewhere gives a finite Phi (exp(-inf) = 0) whose Gaussian
  * derivatives are NaN -- a fit from there ends VP_TERM_NUMERICAL, as the reference's does.  The batch is never aborted.
@@ -129,7 +147,12 @@ enum {
      * update of an (n+1+p)^2 triangle; any m) even where a register-resident kernel set covers m.  The library selects them
      * by itself beyond the largest resident set; the flag exists for memory-lean handles and for the parity tests.  Ignored
      * for models without such a set (they run on the generic kernels, as before). */
-    VP_FLAG_STREAM_ROWS = 1 << 5
+    VP_FLAG_STREAM_ROWS = 1 << 5,
+    /* A descriptor of the kinds 0..4 alone becomes a DEVICE-COLUMN handle too (see "device-column handles" above): its
+     * columns go through device memory instead of registers -- slower than the in-register kernels, but such a handle
+     * takes vp_set_bounds.  No effect on descriptors with a peak / baseline kind (they are device-column handles anyway)
+     * and on vp_batch_create_external. */
+    VP_FLAG_DEVICE_COLUMNS = 1 << 6
 };
 
 /* per-problem status word (0 == the reference's `cached = Some(..)`) */
@@ -263,6 +286,15 @@ int vp_weighted_data(vp_batch *h, void *Yw_out);
  * (host or device pointer according to the handle's flags).
  */
 int vp_set_observations(vp_batch *h, const void *Y);
+
+/* Box bounds on the nonlinear parameters of vp_fit, device-column handles only (see "device-column handles" above).
+ * lower / upper: HOST pointers to doubles whatever the handle's dtype and flags, [q] (per_problem = 0) or [B][q];
+ * -INFINITY / +INFINITY = unbounded on that side; both NULL clears the bounds.  Stays set across vp_fit calls and
+ * vp_set_observations.
+ * VP_ERR_INVALID: a NaN, lower >= upper (fixing a parameter is not supported), exactly one pointer NULL, a stepped fit in
+ * progress.  VP_ERR_UNSUPPORTED: not a device-column handle (create it with VP_FLAG_DEVICE_COLUMNS).  A refusal leaves the
+ * handle, and the bounds it had, as they were. */
+int vp_set_bounds(vp_batch *h, const double *lower, const double *upper, int per_problem);
 
 /* 1/2 ||vec R_b||^2 per problem, always f64 [B] (== MinimizationReport::objective_function) */
 int vp_cost(vp_batch *h, double *cost_out);

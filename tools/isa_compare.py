@@ -9,16 +9,24 @@ LITERAL = r", (0x[0-9a-f]+|-?\d+)$"
 
 
 def kernels_of(lib):
-    """{(code object index, kernel symbol): (instruction lines, resources)}; the libraries compared are linked from the same
-    translation units in the same order, so the index names the same unit in both"""
-    tmp, out = tempfile.mkdtemp(), {}
+    """({(code object index, kernel symbol): (instruction lines, resources)}, padding lines dropped); the libraries compared
+    are linked from the same translation units in the same order, so the index names the same unit in both"""
+    tmp, out, dropped = tempfile.mkdtemp(), {}, 0
     try:
         for n, co in enumerate(code_objects(lib, tmp)):
             res = {k["symbol"].replace(".kd", ""): [k.get(f, 0) for f in RES] for k in kernel_notes(co) if "symbol" in k}
             sym, pcrel = None, 0
+            # objdump prints `...` for a run of zero bytes.  As the LAST line of a kernel it is the padding up to the next
+            # symbol (layout, not this kernel's code) and is dropped and counted; anywhere else it stays and is compared.
+            def drop_trailing_padding():
+                nonlocal dropped
+                if sym and out[(n, sym)][0] and out[(n, sym)][0][-1] == "...":
+                    out[(n, sym)][0].pop()
+                    dropped += 1
             for line in subprocess.run([LLVM + "/llvm-objdump", "-d", co], capture_output=True, text=True, check=True).stdout.splitlines():
                 m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
                 if m:
+                    drop_trailing_padding()
                     sym = m.group(1) if m.group(1) in res else None
                     if sym: out[(n, sym)] = ([], res[sym])
                 elif sym and line.startswith("\t"):
@@ -30,10 +38,11 @@ def kernels_of(lib):
                         ins, pcrel = re.sub(LITERAL, ", <pc-relative>", ins), pcrel - 1
                     else: pcrel = 0
                     out[(n, sym)][0].append(ins)
+            drop_trailing_padding()
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     if not out: raise SystemExit("no kernels found in " + lib)
-    return out
+    return out, dropped
 
 
 def family(sym):
@@ -47,7 +56,7 @@ def family(sym):
     return name
 
 
-before, after = kernels_of(sys.argv[1]), kernels_of(sys.argv[2])
+(before, pad_before), (after, pad_after) = kernels_of(sys.argv[1]), kernels_of(sys.argv[2])
 different, families, diff_families = [], collections.Counter(), collections.Counter()
 for k in sorted(set(before) & set(after)):
     families[family(k[1])] += 1
@@ -56,7 +65,8 @@ for k in sorted(set(before) & set(after)):
         different.append({"code_object": k[0], "kernel": k[1], "instructions_before": len(before[k][0]), "instructions_after": len(after[k][0]),
                           "resources_equal": before[k][1] == after[k][1], "resources_before": dict(zip(RES, before[k][1])),
                           "resources_after": dict(zip(RES, after[k][1]))})
-summary = {"kernels_before": len(before), "kernels_after": len(after), "only_before": sorted(map(list, set(before) - set(after))),
+summary = {"kernels_before": len(before), "kernels_after": len(after), "trailing_padding_lines_dropped": [pad_before, pad_after],
+           "only_before": sorted(map(list, set(before) - set(after))),
            "only_after": sorted(map(list, set(after) - set(before))), "identical": len(set(before) & set(after)) - len(different),
            "different": len(different), "different_with_other_resources": sum(1 for d in different if not d["resources_equal"]),
            "kernels_per_family": dict(sorted(families.items())), "different_per_family": dict(sorted(diff_families.items())),

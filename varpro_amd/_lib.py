@@ -23,6 +23,7 @@ VP_F64, VP_F32 = 0, 1
 VP_FLAG_DEVICE_PTRS, VP_FLAG_T_PER_PROBLEM, VP_FLAG_W_PER_PROBLEM, VP_FLAG_OWN_STREAM = 1, 2, 4, 8
 VP_FLAG_NO_GRID_RECURRENCE = 16
 VP_FLAG_STREAM_ROWS = 32
+VP_FLAG_DEVICE_COLUMNS = 64
 VP_BASIS_SKIP_INVARIANT = 1
 VP_BASIS_CONST, VP_BASIS_EXP_DECAY, VP_BASIS_EXP_RATE, VP_BASIS_EXP_COS, VP_BASIS_SIN_PHASE, VP_BASIS_EXTERNAL = 0, 1, 2, 3, 4, 5
 VP_BASIS_GAUSS, VP_BASIS_LORENTZ, VP_BASIS_LINEAR = 6, 7, 8
@@ -51,6 +52,7 @@ ABI_SYMBOLS = [
     "vp_last_error_detail", "vp_version", "vp_device_count",
     "vp_batch_create_external", "vp_set_params_with_basis", "vp_jacobian_with_derivatives", "vp_evaluate_with_basis",
     "vp_reduce_cost", "vp_fit_begin", "vp_fit_step_with_basis", "vp_fit_end", "vp_fit_active_set", "vp_global_statistics",
+    "vp_set_bounds",
 ]
 
 
@@ -125,6 +127,8 @@ def load():
     lib.vp_batch_destroy.restype = None
     lib.vp_set_params.argtypes = [vp, vp]
     lib.vp_set_observations.argtypes = [vp, vp]
+    if hasattr(lib, "vp_set_bounds"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no bounds)
+        lib.vp_set_bounds.argtypes = [vp, dp, dp, C.c_int]
     lib.vp_params.argtypes = [vp, vp]
     lib.vp_residuals.argtypes = [vp, vp, vp]
     lib.vp_jacobian.argtypes = [vp, vp, vp]

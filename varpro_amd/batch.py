@@ -17,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, bounds as _bounds
 from ._lib import check
 
 try:
@@ -84,6 +84,10 @@ class LevenbergMarquardt:
         return o
 
 
+def _to_host(a):
+    return a.detach().cpu().numpy() if _is_torch(a) else a
+
+
 def _tensors_in(obj):
     if _is_torch(obj):
         yield obj
@@ -128,10 +132,13 @@ def _device_entry(fn):
 
 
 class BatchProblem:
-    def __init__(self, model, Y, x=None, weights=None, epsilon=None, device=0, grid_recurrence=True, stream_rows=False):
+    def __init__(self, model, Y, x=None, weights=None, epsilon=None, device=0, grid_recurrence=True, stream_rows=False,
+                 device_columns=False):
         """model: varpro_amd.SeparableModel; Y: (B, m) or (B, S, m); x: (m,) shared grid or (B, m)
         per-problem grids (default: model.x); weights: None (unit), (m,) or (B, m).
-        grid_recurrence=False sets VP_FLAG_NO_GRID_RECURRENCE (per-row exponentials even on uniform grids)."""
+        grid_recurrence=False sets VP_FLAG_NO_GRID_RECURRENCE (per-row exponentials even on uniform grids).
+        device_columns=True sets VP_FLAG_DEVICE_COLUMNS: a descriptor of the exponential / trigonometric kinds alone becomes a
+        device-column handle too, which takes ``set_bounds``."""
         self.lib = _lib.load()
         self.model = model
         self.n = model.base_function_count()
@@ -162,6 +169,8 @@ class BatchProblem:
         flags = 0 if grid_recurrence else _lib.VP_FLAG_NO_GRID_RECURRENCE
         if stream_rows:  # VP_FLAG_STREAM_ROWS: the length-agnostic fit kernels even where a resident set covers m
             flags |= _lib.VP_FLAG_STREAM_ROWS
+        if device_columns:
+            flags |= _lib.VP_FLAG_DEVICE_COLUMNS
         if self.device_mode:
             flags |= _lib.VP_FLAG_DEVICE_PTRS  # work is enqueued on torch's current stream
         else:
@@ -570,6 +579,22 @@ class BatchProblem:
             Y = Y.contiguous()
         check(self.lib.vp_set_observations(self._h, self._ptr(Y)))
         self._have_params = False
+
+    def set_bounds(self, lower, upper):
+        """Box bounds on the nonlinear parameters of ``fit`` (vp_set_bounds; device-column handles: a model with a peak /
+        baseline kind, or ``device_columns=True``).  lower / upper: arrays of shape (q,) or (B, q); None on a side or an
+        infinite entry means unbounded; ``set_bounds(None, None)`` clears.  The bounds stay set across ``fit`` and
+        ``set_observations``.  The fit iterates on internal parameters (varpro_amd.bounds): every returned parameter lies
+        inside its box, the tolerances of the solver act on the internal parameters, and a start on a bound stays there --
+        start strictly inside.  ValueError: wrong shape, NaN, lower >= upper."""
+        nb = _bounds.normalize(None if lower is None else np.asarray(_to_host(lower), dtype=np.float64),
+                               None if upper is None else np.asarray(_to_host(upper), dtype=np.float64), self.B, self.q)
+        if nb is None:
+            check(self.lib.vp_set_bounds(self._h, None, None, 0))
+            return
+        lo, hi, per_problem = nb
+        dp = C.POINTER(C.c_double)
+        check(self.lib.vp_set_bounds(self._h, lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), int(per_problem)))
 
     def set_rhs_allreduce(self, global_rhs_count, group=None):
         """Shard ONE global fit over ranks by right-hand sides (vp_set_rhs_allreduce): this handle

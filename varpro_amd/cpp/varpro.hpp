@@ -290,7 +290,8 @@ class BatchProblem {
     int n = 0, q = 0;
     BatchProblem() = default;
     BatchProblem(const SeparableModel &model, const std::vector<double> &Y, int64_t B_, int64_t S_,
-                 const std::vector<double> *weights = nullptr, double epsilon = -1.0, int device = 0) {
+                 const std::vector<double> *weights = nullptr, double epsilon = -1.0, int device = 0,
+                 bool device_columns = false) { // device_columns: VP_FLAG_DEVICE_COLUMNS (any descriptor then takes set_bounds)
         m = (int64_t)model.output_len();
         B = B_;
         S = S_;
@@ -298,7 +299,7 @@ class BatchProblem {
         q = model.desc.n_params;
         if ((int64_t)Y.size() != B * S * m) throw std::invalid_argument("Y must hold B*S*m values");
         check(vp_batch_create(&h_, &model.desc, VP_F64, m, S, B, model.x.data(), Y.data(), weights ? weights->data() : nullptr,
-                              epsilon, VP_FLAG_OWN_STREAM, device, nullptr));
+                              epsilon, VP_FLAG_OWN_STREAM | (device_columns ? VP_FLAG_DEVICE_COLUMNS : 0), device, nullptr));
     }
     BatchProblem(const BatchProblem &) = delete;
     BatchProblem &operator=(const BatchProblem &) = delete;
@@ -318,6 +319,15 @@ class BatchProblem {
         if ((int64_t)Y.size() != B * S * m) throw std::invalid_argument("Y must hold B*S*m values");
         check(vp_set_observations(h_, Y.data()));
     }
+    // box bounds of fit() on a device-column handle (vp_set_bounds): q values (one box for all problems) or B*q values
+    // each; +-INFINITY = unbounded on that side.  The bounds stay set until clear_bounds()
+    void set_bounds(const std::vector<double> &lower, const std::vector<double> &upper) {
+        const bool per_problem = (int64_t)lower.size() == B * q && B > 1;
+        if (lower.size() != upper.size() || ((int64_t)lower.size() != q && !per_problem))
+            throw std::invalid_argument("bounds must hold q or B*q values each");
+        check(vp_set_bounds(h_, lower.data(), upper.data(), per_problem ? 1 : 0));
+    }
+    void clear_bounds() { check(vp_set_bounds(h_, nullptr, nullptr, 0)); }
     std::vector<int32_t> status() const {
         std::vector<int32_t> st((size_t)B);
         check(vp_linear_coeffs(h_, nullptr, st.data()));
@@ -626,8 +636,9 @@ class SeparableProblem {
 
   public:
     SeparableProblem(SeparableModel model, const std::vector<double> &Y, int64_t S, std::optional<std::vector<double>> weights,
-                     double epsilon)
-        : model_(std::move(model)), batch_(model_, Y, 1, S, weights ? &*weights : nullptr, epsilon), weights_(std::move(weights)) {
+                     double epsilon, bool device_columns = false)
+        : model_(std::move(model)), batch_(model_, Y, 1, S, weights ? &*weights : nullptr, epsilon, 0, device_columns),
+          weights_(std::move(weights)) {
         set_params(model_.params()); // build(): initial set_params (src/problem/builder.rs:321)
     }
     void set_params(const std::vector<double> &p) { // src/solvers/levmar/mod.rs:42-73
@@ -661,6 +672,8 @@ class SeparableProblemBuilder {
     int64_t S_ = 1;
     std::optional<std::vector<double>> weights_;
     double eps_ = -1.0;
+    bool device_columns_ = false;
+    std::optional<std::pair<std::vector<double>, std::vector<double>>> bounds_;
     SeparableProblemBuilder(SeparableModel m, bool mrhs) : model_(std::move(m)), mrhs_(mrhs) {}
 
   public:
@@ -674,6 +687,12 @@ class SeparableProblemBuilder {
     }
     SeparableProblemBuilder &weights(std::vector<double> w) { return weights_ = std::move(w), *this; }
     SeparableProblemBuilder &epsilon(double e) { return eps_ = std::fabs(e), *this; }
+    // additions to the reference's builder: VP_FLAG_DEVICE_COLUMNS, and box bounds on the nonlinear parameters (q values
+    // each, +-INFINITY = unbounded; the model needs a peak / baseline kind or device_columns())
+    SeparableProblemBuilder &device_columns(bool on = true) { return device_columns_ = on, *this; }
+    SeparableProblemBuilder &bounds(std::vector<double> lower, std::vector<double> upper) {
+        return bounds_ = std::make_pair(std::move(lower), std::move(upper)), *this;
+    }
     SeparableProblem build() {
         if (!Y_) throw SeparableProblemBuilderError("YDataMissing", "Right hand side(s) not provided");
         const size_t xlen = model_.output_len();
@@ -682,7 +701,9 @@ class SeparableProblemBuilder {
             throw SeparableProblemBuilderError("InvalidLengthOfData", "Vectors x and y must have same lengths.");
         if (weights_ && weights_->size() != xlen)
             throw SeparableProblemBuilderError("InvalidLengthOfWeights", "The weights must have the same length as the data y.");
-        return SeparableProblem(model_, *Y_, S_, weights_, eps_);
+        SeparableProblem problem(model_, *Y_, S_, weights_, eps_, device_columns_);
+        if (bounds_) problem.batch().set_bounds(bounds_->first, bounds_->second);
+        return problem;
     }
 };
 

@@ -319,6 +319,10 @@ struct __attribute__((visibility("hidden"))) vp_batch {
     void *col_phi = nullptr, *col_dphi = nullptr; // [B][n][rows], [B][p][rows]; allocated at first use
     int col_look = 8;    // vp_fit: the host reads the active count every col_look steps (vp_debug_set_column_fit; measured)
     int col_nt = 1;      // stores of the column kernel: 1 = non-temporal, 0 = ordinary (vp_debug_set_column_fit; measured)
+    // box bounds of vp_fit (vp_set_bounds): the fit iterates on internal parameters u, alpha = g(u) (vp_cols.hpp bound_map)
+    bool bounded = false;
+    void *d_lo = nullptr, *d_hi = nullptr; // [q] or [B][q] of the handle's dtype, rounded INTO the box
+    int64_t bound_stride = 0;              // 0: one box for all problems, q: per problem
     // batched reverse-communication LM fit of a caller-evaluated model (vp_fit_begin / vp_fit_step_with_basis / vp_fit_end)
     void *d_xf_state = nullptr;      // [B] LM records of the step kernel
     void *d_xf_trial = nullptr;      // [B][q] trial points of the last step
@@ -616,7 +620,9 @@ void fill_cols_params(const vp_batch *h, ColsParams &c) {
 }
 // Phi and dPhi of `alpha_dev` [B][q] into the handle's own buffers, which become the columns of the caller-evaluated path.
 // list / count (device): only these problems, `bound` an upper bound of *count; null: all B
-int fill_own_columns(vp_batch *h, const void *alpha_dev, const int32_t *list, const int32_t *count, int64_t bound) {
+// `internal`: alpha_dev holds the internal parameters of a bounded fit (the bounded column kernel maps them)
+int fill_own_columns(vp_batch *h, const void *alpha_dev, const int32_t *list, const int32_t *count, int64_t bound,
+                     const bool internal = false) {
     const size_t ts = tsize(h->dtype), rows = (size_t)col_rows(h);
     if (int rc = h->ensure(h->col_phi, (size_t)h->B * h->n * rows * ts)) return rc;
     if (h->ext_np > 0)
@@ -629,6 +635,11 @@ int fill_own_columns(vp_batch *h, const void *alpha_dev, const int32_t *list, co
     c.list = list;
     c.count = count;
     c.nt = h->col_nt == 1 ? 1 : 0;
+    if (internal) {
+        c.lo = h->d_lo;
+        c.hi = h->d_hi;
+        c.bound_stride = h->bound_stride;
+    }
     if (list) c.B = bound;
     if (int rc = cols_fill(c)) return fail(rc, "column kernel launch failed");
     h->ext_phi = h->col_phi;
@@ -1338,6 +1349,7 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
         for (int j = 0; j < model->n_basis; ++j)
             if (model->kind[j] == VP_BASIS_GAUSS || model->kind[j] == VP_BASIS_LORENTZ || model->kind[j] == VP_BASIS_LINEAR)
                 devcols = true;
+    if (!ext && (flags & VP_FLAG_DEVICE_COLUMNS)) devcols = true; // ... or any descriptor, on request (the kernel evaluates all kinds)
     vp_model_desc shape_desc;
     int32_t dc_pb[VP_MAX_PAIRS], dc_pp[VP_MAX_PAIRS];
     ExtSpec dc_ext{0, dc_pb, dc_pp};
@@ -1827,6 +1839,12 @@ int vp_basis(vp_batch *h, const void *alpha, void *Phi_out, void *dPhi_out, int 
 namespace {
 // one step of that loop: the LM step on the handle's own columns, the trial points stay on the device; `look`: read the
 // active count (synchronises the stream)
+// d_alpha <- g^-1(d_alpha) (to_internal) or g(d_alpha), in place on the handle's stream
+int transform_alpha(vp_batch *h, const int to_internal) {
+    if (int rc = bounds_transform(h->dtype, h->d_alpha, h->d_lo, h->d_hi, h->bound_stride, h->q, h->B, to_internal, h->stream))
+        return fail(rc, "bounds map kernel launch failed");
+    return VP_ERR_OK;
+}
 int devcols_step(vp_batch *h, const bool look, int64_t &n_active) {
     ExtFitParams p;
     fill_ext_params(h, p);
@@ -1847,14 +1865,22 @@ int devcols_fit(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C_
     if (int rc = xf_begin(h, opts, alpha_inout, 0)) return rc;
     const int64_t limit = 2 * ((int64_t)h->xf_opts.patience * (h->q + 1) + 2);
     Timer tm(h, VP_KERNEL_FIT);
+    // box bounds: the LM drivers iterate on u = g^-1(alpha) -- d_alpha, the trial points and the best points are internal
+    // until the loop has ended; only the column kernel knows
+    const bool bnd = h->bounded;
+    if (bnd)
+        if (int rc = transform_alpha(h, 1)) {
+            h->xf_running = false;
+            return rc;
+        }
     for (int64_t step = 1; step <= limit; ++step) {
         int rc;
         if (h->xf_init) {
-            rc = fill_own_columns(h, h->d_alpha, nullptr, nullptr, h->B);
+            rc = fill_own_columns(h, h->d_alpha, nullptr, nullptr, h->B, bnd);
         } else {
             const int slot = (int)((h->xf_steps + 1) & 1); // what the previous step's LM kernel wrote
             const int64_t bound = h->xf_known_active < h->B ? std::max<int64_t>(h->xf_known_active, 1) : h->B;
-            rc = fill_own_columns(h, h->d_xf_trial, h->d_xf_active + (size_t)slot * h->B, h->d_xf_nactive + slot, bound);
+            rc = fill_own_columns(h, h->d_xf_trial, h->d_xf_active + (size_t)slot * h->B, h->d_xf_nactive + slot, bound, bnd);
         }
         if (rc) {
             h->xf_running = false;
@@ -1869,8 +1895,10 @@ int devcols_fit(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C_
         if (look && nact == 0) break;
     }
     h->xf_running = false;
+    if (bnd) // back to the caller's parameters: the same map as the column kernel's, so alpha is the point of the last columns
+        if (int rc = transform_alpha(h, 0)) return rc;
     after_fit(h);
-    // the handle's state is the fitted point, its columns included
+    // the handle's state is the fitted point, its columns included (unbounded: d_alpha holds alpha again)
     if (int rc = fill_own_columns(h, h->d_alpha, nullptr, nullptr, h->B)) return rc;
     tm.stop();
     return copy_fit_out(h, alpha_inout, C_out, rep);
@@ -1983,6 +2011,49 @@ int vp_fit_trace(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C
     after_fit(h);
     if (int rc2 = copy_fit_out(h, alpha_inout, C_out, rep)) return rc2;
     return tr.finish(h);
+}
+
+int vp_set_bounds(vp_batch *h, const double *lower, const double *upper, int per_problem) {
+    VP_ENTER(h);
+    if (!h->devcols)
+        return fail(VP_ERR_UNSUPPORTED, "vp_set_bounds needs a device-column handle: a descriptor with VP_BASIS_GAUSS / _LORENTZ / "
+                                        "_LINEAR, or any descriptor created with VP_FLAG_DEVICE_COLUMNS");
+    if (h->xf_running) return fail(VP_ERR_INVALID, "vp_set_bounds during a stepped fit");
+    if (!lower && !upper) {
+        h->bounded = false;
+        return VP_ERR_OK;
+    }
+    if (!lower || !upper) return fail(VP_ERR_INVALID, "vp_set_bounds: lower and upper must both be given (or both be NULL)");
+    const size_t count = (size_t)(per_problem ? h->B : 1) * (size_t)h->q;
+    for (size_t i = 0; i < count; ++i)
+        if (std::isnan(lower[i]) || std::isnan(upper[i]) || !(lower[i] < upper[i]))
+            return fail(VP_ERR_INVALID, "vp_set_bounds: every parameter needs lower < upper (no NaN; -INFINITY / +INFINITY = unbounded)");
+    // the box in the handle's dtype, rounded INTO the caller's box: a parameter inside the stored box is inside the caller's
+    const size_t ts = tsize(h->dtype), bytes = count * ts;
+    std::vector<unsigned char> host(2 * bytes);
+    for (size_t i = 0; i < count; ++i) {
+        if (h->dtype == VP_F64) {
+            reinterpret_cast<double *>(host.data())[i] = lower[i];
+            reinterpret_cast<double *>(host.data() + bytes)[i] = upper[i];
+        } else {
+            float lo = (float)lower[i], hi = (float)upper[i];
+            if ((double)lo < lower[i]) lo = std::nextafterf(lo, INFINITY);
+            if ((double)hi > upper[i]) hi = std::nextafterf(hi, -INFINITY);
+            if (!(lo < hi)) return fail(VP_ERR_INVALID, "vp_set_bounds: the box is empty in the handle's fp32");
+            reinterpret_cast<float *>(host.data())[i] = lo;
+            reinterpret_cast<float *>(host.data() + bytes)[i] = hi;
+        }
+    }
+    // (sized for the per-problem form at the first call: a later call may switch forms)
+    if (int rc = h->ensure(h->d_lo, (size_t)h->B * h->q * ts)) return rc;
+    if (int rc = h->ensure(h->d_hi, (size_t)h->B * h->q * ts)) return rc;
+    h->bounded = false; // (until both arrays have arrived)
+    VP_HIP(hipMemcpyAsync(h->d_lo, host.data(), bytes, hipMemcpyHostToDevice, h->stream));
+    VP_HIP(hipMemcpyAsync(h->d_hi, host.data() + bytes, bytes, hipMemcpyHostToDevice, h->stream));
+    VP_HIP(hipStreamSynchronize(h->stream)); // (the staging vector goes out of scope)
+    h->bound_stride = per_problem ? h->q : 0;
+    h->bounded = true;
+    return VP_ERR_OK;
 }
 
 int vp_debug_set_column_fit(vp_batch *h, int look_every, int nontemporal) {

@@ -14,6 +14,11 @@
 // Index list: with `list` / `count` (device pointers) only problems list[0 .. *count) are evaluated -- in a fit that is the
 // active set the LM step kernel maintains, read on the device; the grid covers the host's upper bound of the count and
 // workgroups beyond the count retire at once.
+//
+// Box bounds (vp_set_bounds): during a bounded fit the LM drivers iterate on an INTERNAL vector u, and the bounded sibling
+// of the kernel reads u where the kernel reads alpha, forms alpha_k = g(u_k) per parameter (bound_map below: the MINUIT /
+// lmfit maps), evaluates the basis functions at alpha exactly as the unbounded kernel does and multiplies every stored
+// derivative column by dalpha_k/du_k of its parameter.  Nothing downstream of the columns knows about the bounds.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,9 +44,14 @@ struct ColsParams {
     int64_t B;             // problems (without a list), else the upper bound of *count the grid covers
     const int32_t *list;   // null: problems 0 .. B-1
     const int32_t *count;  // device count of the list (read by the kernel)
+    const void *lo, *hi;   // both non-null: `alpha` holds INTERNAL parameters u, the bounded kernel maps them; [q] or [B][q]
+    int64_t bound_stride;  // 0: one box for all problems, q: per problem
     hipStream_t stream;
 };
 int cols_fill(const ColsParams &p);
+// in place on x [B][q] (the handle's dtype): x <- g^-1(x) (to_internal != 0) or x <- g(x), the maps of bound_map / bound_unmap
+int bounds_transform(int dtype, void *x, const void *lo, const void *hi, int64_t bound_stride, int q, int64_t B, int to_internal,
+                     hipStream_t stream);
 
 namespace cols {
 
@@ -55,6 +65,11 @@ template <typename T> struct ColsArgs {
     const int32_t *list, *count;
     int64_t t_stride, first; // first: problem (or list slot) of workgroup 0
     int m, blocks_per_problem;
+};
+// the bounded kernel's record: `alpha` holds the internal parameters u
+template <typename T> struct ColsBoundArgs : ColsArgs<T> {
+    const T *lo, *hi;     // [q] or [B][bound_stride]; an infinite entry: no bound on that side
+    int64_t bound_stride; // 0: shared
 };
 
 template <typename T> struct Vec;
@@ -92,6 +107,50 @@ __device__ __forceinline__ void store_group(T *__restrict__ col, const int i, co
 template <typename T> __device__ __forceinline__ T cexp(const T x) {
     const T v = texp(x);
     return __builtin_isinf(x) ? (x > T(0) ? x : T(0)) : v;
+}
+
+// ---- box bounds as a smooth re-parameterisation alpha = g(u) (the maps of MINUIT / lmfit), per parameter ----------------
+//   no bound     alpha = u                                   dalpha/du = 1
+//   lo and hi    alpha = lo + (hi - lo)/2 (sin u + 1)        dalpha/du = (hi - lo)/2 cos u
+//   lo only      alpha = lo - 1 + sqrt(u^2 + 1)              dalpha/du = u / sqrt(u^2 + 1)
+//   hi only      alpha = hi + 1 - sqrt(u^2 + 1)              dalpha/du = -u / sqrt(u^2 + 1)
+// The value is clamped to [lo, hi] afterwards: rounding never puts a parameter outside its box (a NaN stays a NaN).  ONE
+// function serves the column kernel and the map kernel, so the alpha a bounded fit returns is the point at which the fit's
+// columns were evaluated; the FMA is explicit so that no compiler decision can make the two differ.
+template <typename T> __device__ __forceinline__ T bound_clamp(const T a, const T lo, const T hi) {
+    return a < lo ? lo : (a > hi ? hi : a);
+}
+template <typename T> __device__ __forceinline__ void bound_map(const T u, const T lo, const T hi, T &alpha, T &dalpha_du) {
+    const bool has_lo = !__builtin_isinf(lo), has_hi = !__builtin_isinf(hi);
+    if (has_lo && has_hi) {
+        T sn, cs;
+        tsincos(u, sn, cs);
+        const T half = T(0.5) * (hi - lo);
+        alpha = bound_clamp(tfma(half, sn + T(1), lo), lo, hi);
+        dalpha_du = half * cs;
+    } else if (has_lo || has_hi) {
+        // beyond 2^27 (fp64) / 2^13 (fp32) u^2 + 1 rounds to u^2: |u| itself, which does not overflow
+        const T au = u < T(0) ? -u : u;
+        const T s = au >= T(sizeof(T) == 8 ? 134217728.0 : 8192.0) ? au : tsqrt(tfma(u, u, T(1)));
+        alpha = bound_clamp(has_lo ? (lo - T(1)) + s : (hi + T(1)) - s, lo, hi);
+        dalpha_du = has_lo ? u / s : -(u / s);
+    } else {
+        alpha = u;
+        dalpha_du = T(1);
+    }
+}
+// u = g^-1(alpha); alpha is clamped to the box first
+__device__ __forceinline__ double tasin(const double x) { return asin(x); }
+__device__ __forceinline__ float tasin(const float x) { return asinf(x); }
+template <typename T> __device__ __forceinline__ T bound_unmap(const T alpha, const T lo, const T hi) {
+    const bool has_lo = !__builtin_isinf(lo), has_hi = !__builtin_isinf(hi);
+    const T a = bound_clamp(alpha, lo, hi);
+    if (has_lo && has_hi) return tasin(bound_clamp(T(2) * (a - lo) / (hi - lo) - T(1), T(-1), T(1)));
+    if (has_lo || has_hi) {
+        const T d = has_lo ? (a - lo) + T(1) : (hi - a) + T(1); // >= 1
+        return tsqrt(d - T(1)) * tsqrt(d + T(1)); // sqrt(d^2 - 1) without the square: finite for every finite d
+    }
+    return a;
 }
 
 // value and derivatives of ONE basis function at one grid value: f, d0 = df/dp0, d1 = df/dp1 (include/varpro_hip.h).
@@ -210,10 +269,108 @@ template <typename T, bool VEC, bool NT> __global__ void __launch_bounds__(256) 
     }
 }
 
+// The bounded sibling: a.alpha holds the INTERNAL parameters u of a bounded fit.  The statements of cols_fill_kernel with
+// alpha_k = g(u_k) in front of each basis function (per problem, not per row: uniform over the workgroup) and the chain rule
+// on its derivative columns.  A kernel of its own, not a template switch of cols_fill_kernel: sharing the body moved
+// operands in the unbounded kernels' instruction text, which stays what it was (profiles/bounds_isa.json).
+template <typename T, bool VEC, bool NT>
+__global__ void __launch_bounds__(256) cols_fill_bounded_kernel(const ColsBoundArgs<T> a) {
+    constexpr int VW = Vec<T>::VW;
+    const unsigned bpp = (unsigned)a.blocks_per_problem;
+    const unsigned slot_local = blockIdx.x / bpp;
+    const int piece = (int)(blockIdx.x - slot_local * bpp);
+    const int i = VW * (piece * 256 + (int)threadIdx.x);
+    const int m = a.m;
+    if (i >= m) return;
+    int64_t b = a.first + (int64_t)slot_local;
+    if (a.list) {
+        if (b >= (int64_t)*a.count) return;
+        b = a.list[b];
+    }
+    const T *tg = a.t + b * a.t_stride + i;
+    T tt[VW];
+    if constexpr (VEC) {
+        const typename Vec<T>::type tv = *reinterpret_cast<const typename Vec<T>::type *>(tg);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) tt[e] = tv[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e) tt[e] = tg[i + e < m ? e : 0];
+    }
+    const int n = a.mdl.n_basis, q = a.mdl.n_params;
+    const T *al = a.alpha + b * q; // (internal parameters)
+    const T *lo = a.lo + b * a.bound_stride, *hi = a.hi + b * a.bound_stride;
+    T *phi = a.phi ? a.phi + b * (int64_t)a.n_phi_cols * m : nullptr;
+    T *dphi = a.dphi ? a.dphi + b * (int64_t)a.n_pairs * m : nullptr;
+    int pair = 0;
+    for (int j = 0; j < n; ++j) {
+        const int kind = a.mdl.kind[j];
+        const int i0 = a.mdl.param[j][0], i1 = a.mdl.param[j][1];
+        T p0 = T(0), p1 = T(0), s0 = T(1), s1 = T(1); // s: dalpha/du
+        if (i0 >= 0) bound_map<T>(al[i0], lo[i0], hi[i0], p0, s0);
+        if (i1 >= 0) bound_map<T>(al[i1], lo[i1], hi[i1], p1, s1);
+        // what the rows of this group share: the reciprocals of the derivative scalings
+        T c0 = T(0), c1 = T(0);
+        if (kind == VP_BASIS_EXP_DECAY) {
+            c0 = T(1) / (p0 * p0);
+        } else if (kind == VP_BASIS_GAUSS) {
+            const T s2 = p1 * p1;
+            c0 = T(1) / s2;
+            c1 = T(1) / (s2 * p1);
+        } else if (kind == VP_BASIS_LORENTZ) {
+            c0 = p1 * p1;
+        }
+        T f[VW], d0[VW], d1[VW];
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+            basis_at<T>(kind, tt[e], p0, p1, c0, c1, f[e], d0[e], d1[e]);
+            d0[e] *= s0;
+            d1[e] *= s1;
+        }
+        if (phi && a.phi_col[j] >= 0) store_group<T, VEC, NT>(phi + (int64_t)a.phi_col[j] * m, i, m, f);
+        if (i0 >= 0) {
+            if (dphi) store_group<T, VEC, NT>(dphi + (int64_t)pair * m, i, m, d0);
+            ++pair;
+        }
+        if (i1 >= 0) {
+            if (dphi) store_group<T, VEC, NT>(dphi + (int64_t)pair * m, i, m, d1);
+            ++pair;
+        }
+    }
+}
+
+// x <- g^-1(x) (INV) or x <- g(x), one thread per parameter of one problem
+template <typename T, bool INV>
+__global__ void __launch_bounds__(256) bounds_map_kernel(T *__restrict__ x, const T *__restrict__ lo, const T *__restrict__ hi,
+                                                         const int64_t bound_stride, const int q, const int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int64_t b = i / q;
+    const int64_t k = b * bound_stride + (i - b * q);
+    if constexpr (INV) {
+        x[i] = bound_unmap<T>(x[i], lo[k], hi[k]);
+    } else {
+        T alpha, scale;
+        bound_map<T>(x[i], lo[k], hi[k], alpha, scale);
+        x[i] = alpha;
+    }
+}
+template <typename T>
+int launch_bounds_transform(void *x, const void *lo, const void *hi, int64_t bound_stride, int q, int64_t B, int to_internal,
+                            hipStream_t stream) {
+    const int64_t total = B * q;
+    if (total <= 0) return VP_ERR_OK;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    if (to_internal) hipLaunchKernelGGL((bounds_map_kernel<T, true>), grid, block, 0, stream, (T *)x, (const T *)lo, (const T *)hi, bound_stride, q, total);
+    else hipLaunchKernelGGL((bounds_map_kernel<T, false>), grid, block, 0, stream, (T *)x, (const T *)lo, (const T *)hi, bound_stride, q, total);
+    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+}
+
 template <typename T> int launch_fill(const ColsParams &p) {
     constexpr int VW = Vec<T>::VW;
     if (p.B <= 0 || p.m <= 0 || (!p.phi && !p.dphi)) return VP_ERR_OK;
     ColsArgs<T> a;
+    const bool bounded = p.lo && p.hi;
     a.mdl = p.model;
     int ncols = 0, npairs = 0;
     for (int j = 0; j < VP_MAX_BASIS; ++j) {
@@ -244,7 +401,20 @@ template <typename T> int launch_fill(const ColsParams &p) {
         const int64_t nb = p.B - first < per_launch ? p.B - first : per_launch;
         a.first = first;
         const dim3 grid((unsigned)(nb * a.blocks_per_problem)), block(256);
-        if (vec) {
+        if (bounded) {
+            ColsBoundArgs<T> ba;
+            static_cast<ColsArgs<T> &>(ba) = a;
+            ba.lo = (const T *)p.lo;
+            ba.hi = (const T *)p.hi;
+            ba.bound_stride = p.bound_stride;
+            if (vec) {
+                if (p.nt) hipLaunchKernelGGL((cols_fill_bounded_kernel<T, true, true>), grid, block, 0, p.stream, ba);
+                else hipLaunchKernelGGL((cols_fill_bounded_kernel<T, true, false>), grid, block, 0, p.stream, ba);
+            } else {
+                if (p.nt) hipLaunchKernelGGL((cols_fill_bounded_kernel<T, false, true>), grid, block, 0, p.stream, ba);
+                else hipLaunchKernelGGL((cols_fill_bounded_kernel<T, false, false>), grid, block, 0, p.stream, ba);
+            }
+        } else if (vec) {
             if (p.nt) hipLaunchKernelGGL((cols_fill_kernel<T, true, true>), grid, block, 0, p.stream, a);
             else hipLaunchKernelGGL((cols_fill_kernel<T, true, false>), grid, block, 0, p.stream, a);
         } else {

@@ -1,5 +1,6 @@
 // the column kernel of device-column handles (vp_cols.hpp): fp64 / fp32 x {16-byte groups, element-wise} x {ordinary,
-// non-temporal stores}.  The sin / cos of the two trigonometric kinds is inlined here (one small kernel per variant).
+// non-temporal stores} x {unbounded, box bounds}, and the two map kernels of bounded fits.  The sin / cos of the two
+// trigonometric kinds is inlined here (one small kernel per variant).
 #define VP_INLINE_SINCOS 1
 #include "vp_cols.hpp"
 
@@ -7,6 +8,12 @@ namespace vp {
 
 int cols_fill(const ColsParams &p) {
     return p.dtype == VP_F64 ? cols::launch_fill<double>(p) : cols::launch_fill<float>(p);
+}
+
+int bounds_transform(int dtype, void *x, const void *lo, const void *hi, int64_t bound_stride, int q, int64_t B, int to_internal,
+                     hipStream_t stream) {
+    return dtype == VP_F64 ? cols::launch_bounds_transform<double>(x, lo, hi, bound_stride, q, B, to_internal, stream)
+                           : cols::launch_bounds_transform<float>(x, lo, hi, bound_stride, q, B, to_internal, stream);
 }
 
 } // namespace vp

@@ -18,8 +18,10 @@ except Exception:  # pragma: no cover
 
 
 class FitPipeline:
-    def __init__(self, model, first_batch, x=None, weights=None, epsilon=None, n_slots=2):
-        """first_batch: a torch CUDA tensor (B, m) or (B, S, m) that fixes the batch shape and the device"""
+    def __init__(self, model, first_batch, x=None, weights=None, epsilon=None, n_slots=2, lower=None, upper=None,
+                 device_columns=False):
+        """first_batch: a torch CUDA tensor (B, m) or (B, S, m) that fixes the batch shape and the device;
+        lower / upper: box bounds of every fit (BatchProblem.set_bounds), set on each slot's handle"""
         if torch is None or not isinstance(first_batch, torch.Tensor) or not first_batch.is_cuda:
             raise ValueError("FitPipeline works on torch CUDA tensors (device-pointer mode)")
         self.device = first_batch.device
@@ -28,8 +30,17 @@ class FitPipeline:
         for st in self.streams:
             st.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(st):
-                self.slots.append(BatchProblem(model, first_batch, x=x, weights=weights, epsilon=epsilon))
+                self.slots.append(BatchProblem(model, first_batch, x=x, weights=weights, epsilon=epsilon,
+                                               device_columns=device_columns))
         self._k = 0
+        if lower is not None or upper is not None:
+            self.set_bounds(lower, upper)
+
+    def set_bounds(self, lower, upper):
+        """box bounds of the fits submitted from now on (BatchProblem.set_bounds on every slot; call it between batches:
+        it waits for each slot's stream)"""
+        for h in self.slots:
+            h.set_bounds(lower, upper)
 
     def submit(self, Y, alpha0, solver=None, want_coefficients=True):
         """enqueue the fit of one batch (asynchronous); returns (alpha, C, report, slot_index).  Y and alpha0 must be
