@@ -1,6 +1,6 @@
 """what do the two (normally empty) re-fit launches behind every vp_fit cost on the headline workload?  Two batches in flight as in
 bench.py, with and without the second launches (vp_debug_set_refit), alternating.  usage: python tools/refit_cost_probe.py"""
-import sys, time
+import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, ".")
 import varpro_amd as vp
@@ -9,8 +9,18 @@ B, m, K = 65536, 1024, 60
 dev = torch.device("cuda", 0)
 hs, gs = [], []
 streams = [torch.cuda.current_stream(dev), torch.cuda.Stream(device=dev)]
-for i in range(2):
+def batch(i):
+    """the i-th batch; with VP_PROBE_DATA=<prefix> it is generated once and kept in <prefix><i>.npz for the processes that follow"""
+    pre = os.environ.get("VP_PROBE_DATA")
+    if pre and os.path.exists("%s%d.npz" % (pre, i)):
+        return dict(np.load("%s%d.npz" % (pre, i)))
     d = synth.double_exp_batch(B, m=m, first_problem=i * B, noise=1e-3)
+    if pre:
+        np.savez("%s%d.tmp.npz" % (pre, i), x=d["x"], Y=d["Y"], tau_guess=d["tau_guess"])
+        os.replace("%s%d.tmp.npz" % (pre, i), "%s%d.npz" % (pre, i))
+    return d
+for i in range(2):
+    d = batch(i)
     mdl = vp.multi_exponential_model(d["x"], d["tau_guess"][0])
     with torch.cuda.stream(streams[i]):
         hs.append(vp.BatchProblem(mdl, torch.from_numpy(d["Y"]).to(dev), x=torch.from_numpy(d["x"]).to(dev)))

@@ -58,6 +58,37 @@ template <typename T, int N, int Q> struct alignas(8) SlotRec {
 #ifndef VP_SLOT_CAP
 #define VP_SLOT_CAP 8
 #endif
+// The critical path of a wave per LM iteration ("Critical path of a wave"): three switches, each bit-identical
+// to its off state (the arithmetic of an evaluation, of the scalar phase and of the refill is untouched).  Measured alone against the
+// parent build, five alternating rounds, two batches in flight (profiles/critical_path_ab_inflight.json): SCALARS 2.039-2.049 ms
+// against 2.083-2.087 (on); LOCAL_CALLS 2.132-2.139 and SKIP_REFILL 2.095-2.100 -- slower alone, and all three together
+// (2.040-2.046) no faster than SCALARS alone: both off.
+#ifndef VP_FIT2_SCALARS
+#define VP_FIT2_SCALARS 1 /* the launch's wave-uniform values (group index -> the LDS pointers of the group; eps, B; the constant column's reflector) are made scalar once: they live in SGPRs instead of VGPRs that the sweep evicts to scratch and reloads -- a VMEM wait -- in every evaluation */
+#endif
+#ifndef VP_FIT2_LOCAL_CALLS
+#define VP_FIT2_LOCAL_CALLS 0 /* the out-of-line functions of the slot loop have internal linkage and take the lane index from the hardware (mbcnt): the compiler sees that they need neither the work-item id nor implicit arguments, and the call sites stop reloading them from scratch.  OFF: +2.4 % alone (the register allocation of the sweep moves with it) */
+#endif
+#ifndef VP_FIT2_SKIP_REFILL
+#define VP_FIT2_SKIP_REFILL 0 /* the scalar phase reports whether any slot of the group terminated; when none did the refill loop and its trailing group_sync are skipped in one branch (a slot finishes once in ~9 evaluations).  OFF: +0.5 % alone, nothing on top of SCALARS -- the refill section's 600 cycles are covered by the partner wave */
+#endif
+#if VP_FIT2_LOCAL_CALLS
+#define VP_SLOT_FN static __noinline__
+#else
+#define VP_SLOT_FN __noinline__
+#endif
+// the lane index from the hardware (two mbcnt): no work-item id needed.  Equal to threadIdx.x & 63 for the 1-D workgroups of 64 * k
+// threads every kernel here is launched with
+__device__ __forceinline__ int slot_lane() {
+    if (!VP_FIT2_LOCAL_CALLS) return lane_id();
+    return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+}
+// a value every lane holds with the same bits, moved to SGPRs
+__device__ __forceinline__ double slot_uni(double x) { return __hiloint2double(uni(__double2hiint(x)), uni(__double2loint(x))); }
+__device__ __forceinline__ float slot_uni(float x) { return __int_as_float(uni(__float_as_int(x))); }
+__device__ __forceinline__ int64_t slot_uni(int64_t x) {
+    return (int64_t)(((uint64_t)(uint32_t)uni((int)((uint64_t)x >> 32)) << 32) | (uint64_t)(uint32_t)uni((int)(uint32_t)x));
+}
 // slots per group: what the LDS of a CU holds next to the shared grid -- per slot one data column and one LM record (REC
 // bytes: a wide model's records are not small change at 24 rows per lane), plus 3 KiB of constants / exchange area
 template <typename T, int R, int W, int NG, int BLOCKS_PER_CU, int REC = 0> constexpr int fit2_slots() {
@@ -141,11 +172,12 @@ __device__ __forceinline__ T fill_slot_column(const T *__restrict__ yp, const in
 // (Re)fill slot `s` of a wave with problem `prob` (wave-uniform; < 0 marks the slot empty).  Out of line: executed once
 // per fit, its register needs must not shape the allocation of the LM loop.
 template <typename T, int N, int Q, int R, int W, int PADM>
-__device__ __noinline__ void slot_fill(VP_LDS SlotRec<T, N, Q> *rec, VP_LDS T *s_col, VP_LDS const T *s_t,
+__device__ VP_SLOT_FN void slot_fill(VP_LDS SlotRec<T, N, Q> *rec, VP_LDS T *s_col, VP_LDS const T *s_t,
                                        VP_LDS const SlotConsts<T> *k, VP_LDS unsigned char *xch, const int prob,
                                        const T h0_beta, const T h0_u, const T h0_g) {
     using G = Grp<W>;
     G grp = G::make((unsigned char *)xch);
+    if constexpr (W == 1) grp.lane = grp.gl = slot_lane();
     const int lane = grp.gl; // group lane
     // W > 1, barrier on entry: (i) every wave decides from the slot's record whether to call this function -- the
     // record must not change before ALL waves have read it (a wave that saw prob = -1 early would skip the call and
@@ -223,8 +255,8 @@ __device__ __noinline__ void slot_fill(VP_LDS SlotRec<T, N, Q> *rec, VP_LDS T *s
 // _inl: the body, inlined into its caller (vp_fitg.hpp: one call site per wave role; out of line its 81 callee-saved
 // VGPRs were stored and reloaded around every call -- 4 % of configs[4]'s launch).
 template <typename T, int N, int Q, int GS, typename TO = T, bool GRAM = false>
-__device__ __forceinline__ void slot_scalar_phase_inl(VP_LDS SlotRec<T, N, Q> *recs, VP_LDS const SlotConsts<T, TO> *k, const bool act = true) {
-    const int lane = lane_id();
+__device__ __forceinline__ bool slot_scalar_phase_inl(VP_LDS SlotRec<T, N, Q> *recs, VP_LDS const SlotConsts<T, TO> *k, const bool act = true,
+                                                      const int lane = lane_id()) {
 #ifdef VP_FIT2_CLOCKS
     long long sc0_ = __builtin_amdgcn_s_memtime();
     const bool sck_on_ = blockIdx.x == 0 && (threadIdx.x >> 6) == 0;
@@ -237,7 +269,7 @@ __device__ __forceinline__ void slot_scalar_phase_inl(VP_LDS SlotRec<T, N, Q> *r
 #else
 #define VP_SCK(i)
 #endif
-    if (!(act && lane < GS && recs[lane].prob >= 0)) return;
+    if (!(act && lane < GS && recs[lane].prob >= 0)) return false;
     VP_LDS SlotRec<T, N, Q> *s = recs + lane;
     const T ftol = k->ftol, xtol = k->xtol, gtol = k->gtol, stepbound = k->stepbound;
     const int scale_diag = k->scale_diag, max_fev = k->max_fev, m = k->m;
@@ -499,12 +531,22 @@ __device__ __forceinline__ void slot_scalar_phase_inl(VP_LDS SlotRec<T, N, Q> *r
         }
     }
     VP_SCK(5);
+    return term != 0; // this lane's slot terminated (its results are written; the caller refills it)
 }
 
+#if VP_FIT2_SKIP_REFILL
+// returns (wave-uniform) whether ANY slot of the group terminated in this pass: the caller's refill section has work
 template <typename T, int N, int Q, int GS, typename TO = T, bool GRAM = false>
-__device__ __noinline__ void slot_scalar_phase(VP_LDS SlotRec<T, N, Q> *recs, VP_LDS const SlotConsts<T, TO> *k, const bool act = true) {
-    slot_scalar_phase_inl<T, N, Q, GS, TO, GRAM>(recs, k, act);
+__device__ VP_SLOT_FN int slot_scalar_phase(VP_LDS SlotRec<T, N, Q> *recs, VP_LDS const SlotConsts<T, TO> *k, const bool act = true) {
+    const bool done = slot_scalar_phase_inl<T, N, Q, GS, TO, GRAM>(recs, k, act, slot_lane());
+    return __builtin_amdgcn_ballot_w64(done) != 0 ? 1 : 0;
 }
+#else
+template <typename T, int N, int Q, int GS, typename TO = T, bool GRAM = false>
+__device__ VP_SLOT_FN void slot_scalar_phase(VP_LDS SlotRec<T, N, Q> *recs, VP_LDS const SlotConsts<T, TO> *k, const bool act = true) {
+    (void)slot_scalar_phase_inl<T, N, Q, GS, TO, GRAM>(recs, k, act, slot_lane());
+}
+#endif
 
 #ifndef VP_LONE_TAIL_LINKAGE
 #define VP_LONE_TAIL_LINKAGE __forceinline__
@@ -851,7 +893,7 @@ template <typename T, class M, int W> inline constexpr bool fit2_self_rescue_v =
 // 160-register column array and spill slots became part of the slot kernel's own frame and the hot loop ran 2 % slower
 // (113 instead of 42 spilled VGPRs in the kernel's metadata, 2.10 instead of 2.065 ms per step with two batches in flight)
 template <typename T, class M, int R>
-__device__ __noinline__ void fit2_refit_flagged(const FitArgs<T, M> *a, const int64_t b, T *s_t, T *s_y, LmState<T, M::N, M::Q> *st) {
+__device__ VP_SLOT_FN void fit2_refit_flagged(const FitArgs<T, M> *a, const int64_t b, T *s_t, T *s_y, LmState<T, M::N, M::Q> *st) {
     (void)fit_problem<T, M, R, 1, false, 0, true, false>(*a, b, s_t, s_y, nullptr, nullptr, st, false);
 }
 
@@ -870,7 +912,8 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
     using Rec = SlotRec<T, N, Q>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *s_t = reinterpret_cast<T *>(smem_raw);
-    const int gi = (W == 1) ? (int)(threadIdx.x >> 6) : 0; // group within the workgroup
+    // group within the workgroup (wave-uniform: as a scalar, every LDS pointer derived from it is one too)
+    const int gi = (W == 1) ? (VP_FIT2_SCALARS ? uni((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6)) : 0;
     T *s_y = s_t + MP + (size_t)gi * GS * MP;
     Rec *recs_all = reinterpret_cast<Rec *>(s_t + MP + (size_t)NG * GS * MP);
     Rec *recs = recs_all + (size_t)gi * GS;
@@ -894,10 +937,11 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
     int64_t B_;
     {
         const FitArgs<T, M> &a = args.f;
-        m_ = a.m;
-        eps_ = a.eps;
-        uniform_ = a.grid_uniform;
-        B_ = a.B;
+        // (the kernel's arguments live in memory -- the re-fit takes their address -- so what is read from them arrives in VGPRs)
+        m_ = VP_FIT2_SCALARS ? uni(a.m) : a.m;
+        eps_ = VP_FIT2_SCALARS ? slot_uni(a.eps) : a.eps;
+        uniform_ = VP_FIT2_SCALARS ? uni(a.grid_uniform) : a.grid_uniform;
+        B_ = VP_FIT2_SCALARS ? slot_uni((int64_t)a.B) : a.B;
         // ---- the shared grid (every group writes the same values: no ownership split needed) + the constants ----
         T tmp[R];
         load_rows<T, R, W>(a.t, m_, lane, vec_aligned<T>(a.t, m_), tmp);
@@ -938,7 +982,15 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
     src.lane = lane;
     src.vec = true;
     src.set_uniform(uniform_ != 0);
-    const ConstReflector<T> h0 = make_const_reflector<T, R, Src, G>(src, grp);
+    const ConstReflector<T> h0 = [&]() __attribute__((always_inline)) {
+        ConstReflector<T> h = make_const_reflector<T, R, Src, G>(src, grp);
+        if constexpr (VP_FIT2_SCALARS != 0) { // (group_sum / group_bcast leave the same bits in every lane)
+            h.beta = slot_uni(h.beta);
+            h.u = slot_uni(h.u);
+            h.g = slot_uni(h.g);
+        }
+        return h;
+    }();
     const M mdl = args.f.mdl;
     if (threadIdx.x == 0) kc->pre_delta = src.uniform ? src.delta : T(0);
     __syncthreads();
@@ -1046,7 +1098,12 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
         VP_CK2(0);
 
         // =============================== SCALAR phase: lane s of wave 0 <-> slot s ===============================
+#if VP_FIT2_SKIP_REFILL
+        int any_done = 1;
+        if (grp.wave == 0) any_done = slot_scalar_phase<T, N, Q, GS>((VP_LDS Rec *)recs, (VP_LDS const SlotConsts<T> *)kc);
+#else
         if (grp.wave == 0) slot_scalar_phase<T, N, Q, GS>((VP_LDS Rec *)recs, (VP_LDS const SlotConsts<T> *)kc);
+#endif
         group_sync();
         VP_CK2(1);
 
@@ -1061,6 +1118,23 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
             }
             __syncthreads();
         }
+#if VP_FIT2_SKIP_REFILL
+        if constexpr (W > 1) {
+            // (every wave takes the branch below on the same LDS values, read after the barrier above: the slot_fill barrier rule)
+            any_done = 0;
+            for (int s = 0; s < GS; ++s) any_done |= (uni(s_pop[s]) != -1) ? 1 : 0;
+        } else {
+            any_done = uni(any_done);
+        }
+        if (any_done == 0) {
+            // nothing finished: no slot to write out or refill, nactive / queue_dry unchanged
+#ifdef VP_FIT2_CLOCKS
+            ck[3] += 1;
+#endif
+            VP_CK2(2);
+            continue;
+        }
+#endif
 #pragma nounroll
         for (int s = 0; s < GS; ++s) {
             if (uni(recs[s].prob) < 0 || uni(recs[s].term) == 0) continue;
@@ -1081,13 +1155,13 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
         group_sync();
         VP_CK2(2);
 #ifndef VP_NO_LONE_TAIL
-        if constexpr (W == 1) {
+        if constexpr (W == 1 && GS > 1) { // (one slot: queue_dry is only ever set as nactive falls to 0 -- the lone tail cannot be reached)
             if (queue_dry && nactive == 1) break; // ONE fit left and nothing to refill from: finish it below
         }
 #endif
     }
 #ifndef VP_NO_LONE_TAIL
-    if constexpr (W == 1) {
+    if constexpr (W == 1 && GS > 1) {
         // the wave's last fit runs the fit_kernel way (fit2_lone_tail) -- as the kernel's exit path: nothing of the slot
         // loop is live across the call
         if (nactive == 1) {
@@ -1126,7 +1200,7 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
 #ifdef VP_FIT2_CLOCKS
     if (args.f.trace && blockIdx.x == 0 && threadIdx.x == 0) {
         double *tr = args.f.trace + (size_t)(args.f.trace_rows - 1) * (Q + 4);
-        for (int i = 0; i < 3; ++i) tr[i] = (double)ck[i];
+        for (int i = 0; i < 4; ++i) tr[i] = (double)ck[i]; // vector | scalar | refill clocks, then the count of skipped refill sections
         // (row trace_rows - 2: the scalar phase's sections -- record load | update + termination tests | gradient test, diag |
         // lmpar | predicted reduction, trial point | write-back, results)
         double *tr2 = args.f.trace + (size_t)(args.f.trace_rows - 2) * (Q + 4);
