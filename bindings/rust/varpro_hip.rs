@@ -56,6 +56,8 @@ pub const VP_FLAG_OWN_STREAM: i32 = 8;
 pub const VP_FLAG_NO_GRID_RECURRENCE: i32 = 16;
 /// a descriptor of the kinds 0..4 alone becomes a device-column handle (it then takes `vp_set_bounds`)
 pub const VP_FLAG_DEVICE_COLUMNS: i32 = 64;
+/// `vp_search`: the candidates are `[B][K][q]`, one set per problem
+pub const VP_SEARCH_PER_PROBLEM: i32 = 1;
 
 #[link(name = "varpro_hip")]
 extern "C" {
@@ -72,6 +74,10 @@ extern "C" {
     pub fn vp_set_observations(h: *mut vp_batch, y: *const c_void) -> i32;
     /// box bounds of `vp_fit` on a device-column handle: host doubles `[q]` or `[B][q]`, infinite = unbounded, both null clears
     pub fn vp_set_bounds(h: *mut vp_batch, lower: *const f64, upper: *const f64, per_problem: i32) -> i32;
+    /// start-point search: per problem the best of `k` candidates (`[K][q]`, or `[B][K][q]` with `VP_SEARCH_PER_PROBLEM`) by
+    /// the projected objective; leaves the handle in the state of `vp_set_params(h, alpha_out)`.  Outputs may be null.
+    pub fn vp_search(h: *mut vp_batch, cand: *const c_void, k: i64, flags: i32, alpha_out: *mut c_void,
+        index_out: *mut i32, cost_out: *mut f64) -> i32;
     pub fn vp_cost(h: *mut vp_batch, cost_out: *mut f64) -> i32;
     pub fn vp_evaluate(h: *mut vp_batch, alpha: *const c_void, r: *mut c_void, j: *mut c_void, c: *mut c_void,
         cost: *mut f64, status: *mut i32) -> i32;

@@ -296,6 +296,43 @@ int vp_set_observations(vp_batch *h, const void *Y);
  * handle, and the bounds it had, as they were. */
 int vp_set_bounds(vp_batch *h, const double *lower, const double *upper, int per_problem);
 
+/*
+ * Start-point search: rank K candidate parameter vectors per problem ON THE DEVICE and leave the best one in the handle.
+ * Every fit starts from a guess (vp_fit's alpha_inout; the reference's initial parameters, src/problem/builder.rs:116); with
+ * variable projection only the q nonlinear parameters need one, and the value of a guess is the projected objective
+ * 1/2 ||P_perp(alpha) y_w||^2 -- what vp_cost returns after vp_set_params(alpha).
+ *   cand       the handle's dtype and address space; [K][q] shared by all problems (flags = 0) or [B][K][q] with
+ *              VP_SEARCH_PER_PROBLEM; K >= 1
+ *   alpha_out  [B][q]  per problem the candidate with the smallest 1/2 ||vec R_b||^2 (summed over the S right-hand sides)
+ *   index_out  [B]     its index; ties go to the lowest index among the candidates that are equal in the device's arithmetic
+ *   cost_out   [B] f64 the cost of the EVALUATION at the winner (below), not the ranking score: it has vp_evaluate's accuracy,
+ *                      not that of a difference of squares
+ * Each output may be NULL.  Afterwards the handle's state is exactly that of vp_set_params(h, alpha_out): vp_params,
+ * vp_linear_coeffs, vp_residuals, vp_cost and status refer to the winners.
+ * Candidates whose Phi is not finite (a NaN; sigma = 0 on a grid point) never win while another candidate of the problem is
+ * finite.  A problem without a finite candidate gets index_out = -1 and its candidate 0 in alpha_out, and its status is
+ * latched non-zero as by vp_set_params.  The batch is never aborted.  Bounds (vp_set_bounds) are not consulted: candidates
+ * are taken as given, as in vp_set_params.
+ * Two routes.  Candidates, grid and weights shared by the batch (and m >= n): the K bases are factored once -- the column
+ * kernel evaluates the candidates, one workgroup each orthonormalises their weighted columns (a direction whose remainder
+ * is <= 64 eps of its column's norm is dropped: the score of the minimum-norm solution) -- and the ranking is ONE matrix
+ * product (B S x m)(m x K n) with the running maximum of sum_j (q_kj . y_w)^2 in its epilogue, then one evaluation at the
+ * winners (measured: DESIGN.md section 3g).  Anything per problem (candidates, grid, weights) and m < n: K cost-only
+ * evaluations through the handle's own kernels with a running minimum on the device, then the evaluation at the winners.
+ * "Not finite" is decided by the ELEMENTS of W Phi on both routes: the shared route scales a column by its largest
+ * magnitude before it squares anything, so a finite column of any size is ranked.
+ * Device-pointer handles stay asynchronous on both routes, with one exception: the scratch of the shared route is sized by
+ * K and grown on demand -- the FIRST call, and any call with a larger K (or a first call with S > 1), allocates, and
+ * replacing a smaller block frees it, which synchronises the device.  Calls with the same or a smaller K enqueue only.
+ * Every descriptor handle is accepted (in-register and device-column, both dtypes, any S, any m).
+ * VP_ERR_INVALID: null cand, K < 1, an unknown flag, a stepped fit in progress.  VP_ERR_UNSUPPORTED: a caller-evaluated
+ * handle (the device cannot evaluate the model), right-hand sides sharded over ranks (vp_set_rhs_allreduce).  A refusal
+ * leaves the handle as it was.
+ */
+enum { VP_SEARCH_PER_PROBLEM = 1 };
+int vp_search(vp_batch *h, const void *cand, int64_t K, int flags,
+              void *alpha_out, int32_t *index_out, double *cost_out);
+
 /* 1/2 ||vec R_b||^2 per problem, always f64 [B] (== MinimizationReport::objective_function) */
 int vp_cost(vp_batch *h, double *cost_out);
 

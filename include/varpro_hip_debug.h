@@ -48,6 +48,13 @@ int vp_debug_set_refit(vp_batch *h, int enabled);
  */
 int vp_debug_set_column_fit(vp_batch *h, int look_every, int nontemporal);
 
+/*
+ * Measurement of vp_search's shared route (tools/search_probe.py): with vp_set_timing(h, 1) the last vp_search leaves the
+ * hipEvent times of its four stages in ms_out -- { candidate columns, orthonormalisation, ranking product, evaluation at
+ * the winners } -- in milliseconds; -1 before the first such call.
+ */
+int vp_debug_search_ms(vp_batch *h, float ms_out[4]);
+
 #ifdef __cplusplus
 }
 #endif

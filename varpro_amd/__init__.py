@@ -10,10 +10,11 @@ Host-side mirror of the reference's public surface over hand-written HIP kernels
 There is no CPU fallback: every compute call runs on the GPU through ``lib/libvarpro_hip.so``
 (C ABI in include/varpro_hip.h) or raises.
 """
-from . import bounds  # noqa: F401
+from . import bounds, search  # noqa: F401
 from ._lib import VarproHipError, VarproHipUnavailable, device_count, load as load_library  # noqa: F401
 from .batch import BatchProblem, LevenbergMarquardt, REPORT_DTYPE  # noqa: F401
 from .pipeline import FitPipeline  # noqa: F401
+from .search import candidate_grid  # noqa: F401
 from .model import (ClosureModel, ExternalModel, ModelBuildError, ModelError, SeparableModel,  # noqa: F401
                     SeparableModelBuilder, basis, multi_exponential_model)
 from .problem import SeparableProblem, SeparableProblemBuilder, SeparableProblemBuilderError  # noqa: F401

@@ -25,6 +25,7 @@ VP_FLAG_NO_GRID_RECURRENCE = 16
 VP_FLAG_STREAM_ROWS = 32
 VP_FLAG_DEVICE_COLUMNS = 64
 VP_BASIS_SKIP_INVARIANT = 1
+VP_SEARCH_PER_PROBLEM = 1
 VP_BASIS_CONST, VP_BASIS_EXP_DECAY, VP_BASIS_EXP_RATE, VP_BASIS_EXP_COS, VP_BASIS_SIN_PHASE, VP_BASIS_EXTERNAL = 0, 1, 2, 3, 4, 5
 VP_BASIS_GAUSS, VP_BASIS_LORENTZ, VP_BASIS_LINEAR = 6, 7, 8
 VP_FIT_DERIVATIVES_ON_ACCEPT = 1
@@ -52,12 +53,13 @@ ABI_SYMBOLS = [
     "vp_last_error_detail", "vp_version", "vp_device_count",
     "vp_batch_create_external", "vp_set_params_with_basis", "vp_jacobian_with_derivatives", "vp_evaluate_with_basis",
     "vp_reduce_cost", "vp_fit_begin", "vp_fit_step_with_basis", "vp_fit_end", "vp_fit_active_set", "vp_global_statistics",
-    "vp_set_bounds",
+    "vp_set_bounds", "vp_search",
 ]
 
 
 # test hooks (include/varpro_hip_debug.h): exported by the library, not part of the drop-in boundary
-DEBUG_SYMBOLS = ["vp_debug_gram_evaluate", "vp_debug_lmpar_gram", "vp_debug_set_refit", "vp_debug_set_column_fit"]
+DEBUG_SYMBOLS = ["vp_debug_gram_evaluate", "vp_debug_lmpar_gram", "vp_debug_set_refit", "vp_debug_set_column_fit",
+                 "vp_debug_search_ms"]
 
 
 class VarproHipUnavailable(ImportError):
@@ -129,6 +131,9 @@ def load():
     lib.vp_set_observations.argtypes = [vp, vp]
     if hasattr(lib, "vp_set_bounds"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no bounds)
         lib.vp_set_bounds.argtypes = [vp, dp, dp, C.c_int]
+    if hasattr(lib, "vp_search"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no search)
+        lib.vp_search.argtypes = [vp, vp, C.c_int64, C.c_int, vp, vp, vp]
+        lib.vp_debug_search_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.vp_params.argtypes = [vp, vp]
     lib.vp_residuals.argtypes = [vp, vp, vp]
     lib.vp_jacobian.argtypes = [vp, vp, vp]

@@ -423,6 +423,45 @@ class BatchProblem:
             Cm = Cm.reshape(self.B, self.n)
         return a, Cm, rep
 
+    # ---- start-point search (vp_search) ----
+    @_device_entry
+    def search(self, candidates, per_problem=False):
+        """Rank candidate parameter vectors per problem on the device (vp_search) -> ``(alpha (B, q), index (B,) int32,
+        cost (B,) float64)``: per problem the candidate with the smallest projected objective 1/2 ||r||^2 (summed over the
+        right-hand sides), its index (lowest among equal ones; -1 where no candidate is finite -- alpha is then candidate
+        0) and the cost of the evaluation there.  candidates: (K, q) shared by all problems (``candidate_grid`` builds
+        one), or (B, K, q) with per_problem=True.  Afterwards the handle is in the state of ``set_params(alpha)``."""
+        c = self._as_array(candidates)
+        if per_problem:
+            if c.ndim != 3 or int(c.shape[0]) != self.B or int(c.shape[2]) != self.q:
+                raise ValueError("per-problem candidates must be (B, K, q)")
+            K = int(c.shape[1])
+        else:
+            if c.ndim == 1 and self.q == 1:
+                c = c.reshape(-1, 1)
+            if c.ndim != 2 or int(c.shape[1]) != self.q:
+                raise ValueError("candidates must be (K, q)")
+            K = int(c.shape[0])
+        a = self._empty((self.B, self.q))
+        idx = self._empty((self.B,), np.int32)
+        cost = self._empty((self.B,), np.float64)
+        check(self.lib.vp_search(self._h, self._ptr(c), K, _lib.VP_SEARCH_PER_PROBLEM if per_problem else 0, self._ptr(a),
+                                 self._ptr(idx), self._ptr(cost)))
+        self._have_params = True
+        return a, idx, cost
+
+    def fit_from_search(self, candidates, solver=None, per_problem=False):
+        """``search(candidates)`` then ``fit`` from the winners: (alpha, C, report) as ``fit`` returns them"""
+        a, _idx, _cost = self.search(candidates, per_problem=per_problem)
+        return self.fit(a, solver)
+
+    def search_stage_ms(self):
+        """measurement (include/varpro_hip_debug.h:vp_debug_search_ms): with ``set_timing(True)``, the milliseconds of the
+        last shared-route ``search``: [candidate columns, orthonormalisation, ranking product, evaluation at the winners]"""
+        ms = (C.c_float * 4)()
+        check(self.lib.vp_debug_search_ms(self._h, ms))
+        return [float(v) for v in ms]
+
     # ---- batched fit of a caller-evaluated model by reverse communication (vp_fit_begin / _step_with_basis / _end) ----
     @_device_entry
     def fit_begin(self, alpha0, solver=None, derivatives_on_accept=False):

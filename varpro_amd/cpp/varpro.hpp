@@ -328,6 +328,21 @@ class BatchProblem {
         check(vp_set_bounds(h_, lower.data(), upper.data(), per_problem ? 1 : 0));
     }
     void clear_bounds() { check(vp_set_bounds(h_, nullptr, nullptr, 0)); }
+    // start-point search (vp_search): per problem the best of K candidates by the projected objective; the handle is then
+    // in the state of set_params(result.alpha).  candidates: K*q values shared by all problems, or B*K*q with per_problem
+    struct SearchResult {
+        std::vector<double> alpha;  // [B][q]
+        std::vector<int32_t> index; // [B], -1: no finite candidate (alpha is then candidate 0)
+        std::vector<double> cost;   // [B]
+    };
+    SearchResult search(const std::vector<double> &candidates, int64_t K, bool per_problem = false) {
+        if (K < 1 || (int64_t)candidates.size() != (per_problem ? B : 1) * K * q)
+            throw std::invalid_argument("candidates must hold K*q values (B*K*q per problem)");
+        SearchResult r{std::vector<double>((size_t)(B * q)), std::vector<int32_t>((size_t)B), std::vector<double>((size_t)B)};
+        check(vp_search(h_, candidates.data(), K, per_problem ? VP_SEARCH_PER_PROBLEM : 0, r.alpha.data(), r.index.data(),
+                        r.cost.data()));
+        return r;
+    }
     std::vector<int32_t> status() const {
         std::vector<int32_t> st((size_t)B);
         check(vp_linear_coeffs(h_, nullptr, st.data()));

@@ -19,6 +19,7 @@
 #include "vp_mrhs.hpp"
 #include "vp_gstats.hpp"
 #include "vp_cols.hpp"
+#include "vp_search.hpp"
 
 using namespace vp;
 
@@ -263,6 +264,23 @@ struct __attribute__((visibility("hidden"))) vp_batch {
         ptr = static_cast<T *>(mem);
         return 0;
     }
+    // scratch whose size depends on a call's arguments (vp_search): grown on demand, the smaller block is released
+    template <typename T> int grow(T *&ptr, size_t &cap, size_t bytes) {
+        if (ptr && cap >= bytes) return 0;
+        if (ptr) {
+            for (size_t i = 0; i < owned_dev.size(); ++i)
+                if (owned_dev[i] == (void *)ptr) {
+                    owned_dev.erase(owned_dev.begin() + (std::ptrdiff_t)i);
+                    break;
+                }
+            (void)hipFree(ptr);
+            ptr = nullptr;
+            cap = 0;
+        }
+        if (int rc = alloc(ptr, bytes ? bytes : 1)) return rc;
+        cap = bytes;
+        return 0;
+    }
     // device state (== SeparableProblem + CachedCalculations for the whole batch)
     void *d_t = nullptr, *d_w = nullptr, *d_yw = nullptr;
     void *d_alpha = nullptr;          // [B][q]
@@ -337,6 +355,13 @@ struct __attribute__((visibility("hidden"))) vp_batch {
     int xf_flags = 0;
     int64_t xf_steps = 0;
     vp_lm_opts xf_opts = {};
+    // vp_search (vp_search.hpp): the candidates' columns, their orthonormal bases, the marks of non-finite candidates, the
+    // winners, the score matrix (S > 1) and the candidate loop's running minimum
+    void *d_srch_phi = nullptr, *d_srch_q = nullptr, *d_srch_scores = nullptr;
+    int32_t *d_srch_bad = nullptr, *d_srch_index = nullptr;
+    double *d_srch_best = nullptr;
+    size_t srch_phi_cap = 0, srch_q_cap = 0, srch_scores_cap = 0, srch_bad_cap = 0;
+    float srch_ms[4] = {-1.f, -1.f, -1.f, -1.f}; // vp_set_timing: the shared route's four stages of the last vp_search
     // flag-and-refit of single-RHS fits (vp_fit.hpp jac_not_finite; rescue_refit below)
     int32_t *d_rescue = nullptr; // [2 + B]: two ping-pong counters + the flagged problems of the running fit
     void *d_rescue_ws = nullptr; // kRescueBlocks workspace slots of the generic fit kernel
@@ -2053,6 +2078,142 @@ int vp_set_bounds(vp_batch *h, const double *lower, const double *upper, int per
     VP_HIP(hipStreamSynchronize(h->stream)); // (the staging vector goes out of scope)
     h->bound_stride = per_problem ? h->q : 0;
     h->bounded = true;
+    return VP_ERR_OK;
+}
+
+// ---- start-point search (vp_search.hpp) ---------------------------------------------------------------------------------
+namespace {
+
+// hipEvents around the stages of the shared route (vp_set_timing); without timing every call is a no-op
+struct SearchClock {
+    vp_batch *h;
+    hipEvent_t ev[5] = {};
+    int count = 0;
+    explicit SearchClock(vp_batch *h_) : h(h_) {}
+    void mark() {
+        if (!h->timing || count >= 5) return;
+        if (hipEventCreate(&ev[count]) != hipSuccess) return;
+        (void)hipEventRecord(ev[count], h->stream);
+        ++count;
+    }
+    ~SearchClock() {
+        if (count == 5) {
+            (void)hipEventSynchronize(ev[4]);
+            for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&h->srch_ms[i], ev[i], ev[i + 1]);
+        }
+        for (int i = 0; i < count; ++i) (void)hipEventDestroy(ev[i]);
+    }
+};
+
+// shared candidates, shared grid, shared (or no) weights: (a) columns of the K candidates, (b) their orthonormal bases,
+// (c) the ranking product; leaves the winners in d_srch_index
+int search_shared(vp_batch *h, const void *cand_dev, const int64_t K, SearchClock &clk) {
+    const size_t ts = tsize(h->dtype);
+    const int64_t Kpad = (K + 15) / 16 * 16, ldq = (h->m + 15) / 16 * 16;
+    if (Kpad > 0x7fffffff || ldq > 0x7fffffff) return fail(VP_ERR_INVALID, "vp_search: K or m out of range");
+    if (int rc = h->grow(h->d_srch_phi, h->srch_phi_cap, (size_t)K * h->n * h->m * ts)) return rc;
+    if (int rc = h->grow(h->d_srch_q, h->srch_q_cap, (size_t)Kpad * h->n * ldq * ts)) return rc;
+    if (int rc = h->grow(h->d_srch_bad, h->srch_bad_cap, (size_t)Kpad * sizeof(int32_t))) return rc;
+    if (h->S > 1)
+        if (int rc = h->grow(h->d_srch_scores, h->srch_scores_cap, (size_t)h->B * h->S * Kpad * ts)) return rc;
+    clk.mark();
+    ColsParams c;
+    fill_cols_params(h, c);
+    c.model = h->devcols ? h->col_model : h->model;
+    c.t_stride = 0;
+    c.alpha = cand_dev;
+    c.phi = h->d_srch_phi;
+    c.B = K;
+    if (int rc = cols_fill(c)) return fail(rc, "column kernel launch failed");
+    clk.mark();
+    // zero columns beyond m and beyond K; every padded candidate marked, (b) clears the marks of the finite ones
+    VP_HIP(hipMemsetAsync(h->d_srch_q, 0, (size_t)Kpad * h->n * ldq * ts, h->stream));
+    VP_HIP(hipMemsetAsync(h->d_srch_bad, 1, (size_t)Kpad * sizeof(int32_t), h->stream));
+    SearchParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.dtype = h->dtype;
+    p.n = h->n;
+    p.K = (int)K;
+    p.Kpad = (int)Kpad;
+    p.m = (int)h->m;
+    p.ldq = (int)ldq;
+    p.B = h->B;
+    p.S = (int)h->S;
+    p.phi = h->d_srch_phi;
+    p.w = h->d_w;
+    p.Q = h->d_srch_q;
+    p.bad = h->d_srch_bad;
+    p.yw = h->d_yw;
+    p.scores = h->d_srch_scores;
+    p.index = h->d_srch_index;
+    p.stream = h->stream;
+    if (int rc = search_orthonormalize(p)) return fail(rc, "vp_search: orthonormalisation kernel launch failed");
+    clk.mark();
+    if (int rc = search_rank(p)) return fail(rc, "vp_search: ranking kernel launch failed");
+    clk.mark();
+    return VP_ERR_OK;
+}
+
+// everything else: K cost-only evaluations through the handle's own evaluate path and a running minimum
+int search_loop(vp_batch *h, const void *cand_dev, const int64_t K, const int per_problem) {
+    if (K > 0x7fffffff) return fail(VP_ERR_INVALID, "vp_search: K out of range");
+    if (int rc = h->ensure(h->d_srch_best, (size_t)h->B * sizeof(double))) return rc;
+    for (int64_t k = 0; k < K; ++k) {
+        if (int rc = search_gather(h->dtype, cand_dev, K, h->q, per_problem, k, nullptr, h->B, h->d_alpha, h->stream))
+            return fail(rc, "vp_search: gather kernel launch failed");
+        if (h->devcols)
+            if (int rc = fill_own_columns(h, h->d_alpha, nullptr, nullptr, h->B)) return rc;
+        if (int rc = run_evaluate(h, nullptr, nullptr, h->d_C)) return rc;
+        if (int rc = search_loop_update(h->d_cost, h->d_status, k, h->B, h->d_srch_best, h->d_srch_index, h->stream))
+            return fail(rc, "vp_search: update kernel launch failed");
+    }
+    return VP_ERR_OK;
+}
+
+} // namespace
+
+int vp_search(vp_batch *h, const void *cand, int64_t K, int flags, void *alpha_out, int32_t *index_out, double *cost_out) {
+    VP_ENTER(h);
+    if (h->xf_running) return fail(VP_ERR_INVALID, "vp_search during a stepped fit");
+    VP_NOT_EXTERNAL(h, "vp_search");
+    if (h->rhs_allreduce)
+        return fail(VP_ERR_UNSUPPORTED, "vp_search: the handle's right-hand sides are sharded over ranks (vp_set_rhs_allreduce)");
+    if (!cand) return fail(VP_ERR_INVALID, "null cand");
+    if (K < 1) return fail(VP_ERR_INVALID, "vp_search needs K >= 1 candidates");
+    if (flags & ~VP_SEARCH_PER_PROBLEM) return fail(VP_ERR_INVALID, "unknown vp_search flag");
+    const int per_problem = (flags & VP_SEARCH_PER_PROBLEM) ? 1 : 0;
+    const size_t ts = tsize(h->dtype);
+    if (int rc = h->ensure(h->d_srch_index, (size_t)h->B * sizeof(int32_t))) return rc;
+    InBuf cd;
+    if (int rc = cd.init(h, cand, (size_t)(per_problem ? h->B : 1) * (size_t)K * h->q * ts)) return rc;
+    // from here on the cached evaluation is being replaced
+    h->r_valid = false;
+    const bool shared = !per_problem && !(h->flags & (VP_FLAG_T_PER_PROBLEM | VP_FLAG_W_PER_PROBLEM)) && !h->m_user;
+    {
+        SearchClock clk(h);
+        if (shared) {
+            if (int rc = search_shared(h, cd.dptr, K, clk)) return rc;
+        } else {
+            if (int rc = search_loop(h, cd.dptr, K, per_problem)) return rc;
+        }
+        // the winners become the handle's parameters (a problem without a finite candidate: its candidate 0), then the
+        // evaluation of vp_set_params
+        if (int rc = search_gather(h->dtype, cd.dptr, K, h->q, per_problem, -1, h->d_srch_index, h->B, h->d_alpha, h->stream))
+            return fail(rc, "vp_search: gather kernel launch failed");
+        if (h->devcols)
+            if (int rc = fill_own_columns(h, h->d_alpha, nullptr, nullptr, h->B)) return rc;
+        if (int rc = cache_at_alpha(h)) return rc;
+        clk.mark();
+    }
+    if (int rc = copy_out(h, alpha_out, h->d_alpha, (size_t)h->B * h->q * ts)) return rc;
+    if (int rc = copy_out(h, index_out, h->d_srch_index, (size_t)h->B * sizeof(int32_t))) return rc;
+    return copy_out(h, cost_out, h->d_cost, (size_t)h->B * sizeof(double));
+}
+
+int vp_debug_search_ms(vp_batch *h, float ms_out[4]) {
+    VP_ENTER(h);
+    if (!ms_out) return fail(VP_ERR_INVALID, "null ms_out");
+    for (int i = 0; i < 4; ++i) ms_out[i] = h->srch_ms[i];
     return VP_ERR_OK;
 }
 
