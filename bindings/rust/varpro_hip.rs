@@ -51,6 +51,10 @@ pub const VP_BASIS_SIN_PHASE: i32 = 4;
 pub const VP_BASIS_GAUSS: i32 = 6;
 pub const VP_BASIS_LORENTZ: i32 = 7;
 pub const VP_BASIS_LINEAR: i32 = 8;
+/// IRF reconvolution on a uniform grid: `sum_{k<=i} irf_k exp(-(i-k) dt/p0)` (no factor dt); needs `vp_set_irf`
+pub const VP_BASIS_EXP_DECAY_IRF: i32 = 9;
+/// the instrument response itself (no parameters): the scattered-light term
+pub const VP_BASIS_IRF: i32 = 10;
 pub const VP_F64: i32 = 0;
 pub const VP_FLAG_OWN_STREAM: i32 = 8;
 pub const VP_FLAG_NO_GRID_RECURRENCE: i32 = 16;
@@ -74,6 +78,9 @@ extern "C" {
     pub fn vp_set_observations(h: *mut vp_batch, y: *const c_void) -> i32;
     /// box bounds of `vp_fit` on a device-column handle: host doubles `[q]` or `[B][q]`, infinite = unbounded, both null clears
     pub fn vp_set_bounds(h: *mut vp_batch, lower: *const f64, upper: *const f64, per_problem: i32) -> i32;
+    /// instrument response of a handle whose descriptor has an IRF kind: `[m]` or `[B][m]` in the handle's dtype and address
+    /// space, copied by the handle; may be called again to replace it
+    pub fn vp_set_irf(h: *mut vp_batch, irf: *const c_void, per_problem: i32) -> i32;
     /// start-point search: per problem the best of `k` candidates (`[K][q]`, or `[B][K][q]` with `VP_SEARCH_PER_PROBLEM`) by
     /// the projected objective; leaves the handle in the state of `vp_set_params(h, alpha_out)`.  Outputs may be null.
     pub fn vp_search(h: *mut vp_batch, cand: *const c_void, k: i64, flags: i32, alpha_out: *mut c_void,

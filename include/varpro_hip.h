@@ -72,7 +72,12 @@ enum {
     /* peak and baseline kinds, d = t - p0 (see "device-column handles" below) */
     VP_BASIS_GAUSS = 6,     /* exp(-d^2/(2 p1^2))      d/dp0 = f*d/p1^2 ; d/dp1 = f*d^2/p1^3                            */
     VP_BASIS_LORENTZ = 7,   /* p1^2/(d^2 + p1^2)       d/dp0 = 2 p1^2 d/(d^2 + p1^2)^2 ; d/dp1 = 2 p1 d^2/(d^2 + p1^2)^2 */
-    VP_BASIS_LINEAR = 8     /* t                       invariant_function (no parameters): a sloped baseline            */
+    VP_BASIS_LINEAR = 8,    /* t                       invariant_function (no parameters): a sloped baseline            */
+    /* IRF reconvolution kinds (see "IRF reconvolution" below): the handle's instrument response irf (vp_set_irf) on a UNIFORM
+     * grid of step dt, rho = exp(-dt/p0).  Rectangle rule: lag 0 included, NO factor dt (the linear coefficient absorbs it) */
+    VP_BASIS_EXP_DECAY_IRF = 9, /* sum_{k<=i} irf_k rho^(i-k)     d/dp0 = dt/p0^2 sum_{k<=i} (i-k) rho^(i-k) irf_k
+                                   i.e. F_i = irf_i + rho F_{i-1}, H_i = rho (H_{i-1} + F_{i-1}), d/dp0 = dt/p0^2 H_i      */
+    VP_BASIS_IRF = 10           /* irf_i                   invariant (no parameters): the scattered-light term             */
 };
 
 /*
@@ -112,6 +117,21 @@ enum {
  *             - the statistics of a parameter that ends on a bound are those of the unconstrained linearisation at that
  *               point (they do not know about the bound);
  *             - bounds constrain vp_fit only: vp_set_params, vp_evaluate and vp_basis take alpha as given, unclipped.
+ *
+ * IRF reconvolution.  A descriptor that contains VP_BASIS_EXP_DECAY_IRF or VP_BASIS_IRF makes a device-column handle as
+ * well: measured decays (fluorescence lifetimes, ring-down traces) are sum_j c_j exp(-t/tau_j) CONVOLVED with the instrument
+ * response, and "iterative reconvolution" fits exactly this model.  The columns of these two kinds come from a scan kernel of
+ * their own (vp_irf.hpp: one wavefront per problem and function), every other kind of the same descriptor from the column
+ * kernel as before; a model such as c1 (irf * exp tau1) + c2 (irf * exp tau2) + c3 irf + c4, or a mix with a Gaussian, is
+ * one descriptor.  Such a handle needs its response before anything that needs columns: until vp_set_irf has been called,
+ * vp_set_params, vp_evaluate, vp_basis, vp_fit and vp_search answer VP_ERR_INVALID (and the statistics "no parameters set
+ * yet").  The grid must be UNIFORM, shared or per problem: dt_b = (t_b[m-1] - t_b[0]) / (m-1); m = 1 is allowed (the column
+ * is irf_0, the derivative 0).  Host-pointer grids are checked at creation -- |t_i - t_0 - i dt| <= 1e-6 |dt|, else
+ * VP_ERR_INVALID; for device-pointer grids (VP_FLAG_DEVICE_PTRS) uniformity is the CALLER'S CONTRACT: the kernel uses the
+ * two end points only.  tau <= 0, a NaN tau or a non-finite response entry give non-finite columns, latched per problem
+ * like every other non-finite Phi.  Bounds, vp_search and the statistics work as on any device-column handle (a response
+ * per problem sends vp_search down its candidate loop, like a grid per problem).
+ *
  * Parameters for which Phi is not finite (a NaN guess; p1 = 0 with p0 on a grid point: 0 / 0) are latched per problem in
  * status[b], like a caller's non-finite columns; p1 = 0 elsewhere gives a finite Phi (exp(-inf) = 0) whose Gaussian
  * derivatives are NaN -- a fit from there ends VP_TERM_NUMERICAL, as the reference's does.  The batch is never aborted.
@@ -295,6 +315,13 @@ int vp_set_observations(vp_batch *h, const void *Y);
  * progress.  VP_ERR_UNSUPPORTED: not a device-column handle (create it with VP_FLAG_DEVICE_COLUMNS).  A refusal leaves the
  * handle, and the bounds it had, as they were. */
 int vp_set_bounds(vp_batch *h, const double *lower, const double *upper, int per_problem);
+
+/* The instrument response of a handle whose descriptor contains VP_BASIS_EXP_DECAY_IRF / VP_BASIS_IRF (see "IRF
+ * reconvolution" above).  irf: [m] (per_problem = 0) or [B][m], the handle's dtype, a host or device pointer according to
+ * VP_FLAG_DEVICE_PTRS; the handle COPIES it into a buffer it owns (on its stream; device pointers: no synchronisation).  May
+ * be called again to replace the response (the next frame of a stream, with vp_set_observations); every cached evaluation /
+ * fit is invalidated.  VP_ERR_INVALID: null irf, a handle without these kinds, a stepped fit in progress. */
+int vp_set_irf(vp_batch *h, const void *irf, int per_problem);
 
 /*
  * Start-point search: rank K candidate parameter vectors per problem ON THE DEVICE and leave the best one in the handle.

@@ -18,6 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, bounds as _bounds
+from .model import basis as _basis, check_irf as _check_irf, uniform_step as _uniform_step
 from ._lib import check
 
 try:
@@ -133,9 +134,11 @@ def _device_entry(fn):
 
 class BatchProblem:
     def __init__(self, model, Y, x=None, weights=None, epsilon=None, device=0, grid_recurrence=True, stream_rows=False,
-                 device_columns=False):
+                 device_columns=False, irf=None):
         """model: varpro_amd.SeparableModel; Y: (B, m) or (B, S, m); x: (m,) shared grid or (B, m)
         per-problem grids (default: model.x); weights: None (unit), (m,) or (B, m).
+        irf: the instrument response of a model with ``basis.EXP_DECAY_IRF`` / ``basis.IRF``, (m,) shared or (B, m)
+        (``set_irf`` sets or replaces it later); such a model needs a uniform grid.
         grid_recurrence=False sets VP_FLAG_NO_GRID_RECURRENCE (per-row exponentials even on uniform grids).
         device_columns=True sets VP_FLAG_DEVICE_COLUMNS: a descriptor of the exponential / trigonometric kinds alone becomes a
         device-column handle too, which takes ``set_bounds``."""
@@ -193,6 +196,14 @@ class BatchProblem:
                     raise ValueError("InvalidLengthOfWeights")
             elif int(w.shape[0]) != self.m:
                 raise ValueError("InvalidLengthOfWeights")  # src/problem/builder.rs:300-303
+        self.irf_kinds = (not self.external) and any(k in _basis.IRF_KINDS for k in model.kinds)
+        if irf is not None:
+            if not self.irf_kinds:
+                raise ValueError("irf given, but the model has no basis.EXP_DECAY_IRF / basis.IRF function")
+            irf = self._as_array(irf)
+            _check_irf(irf, self.B, self.m)
+        if self.irf_kinds and not self.device_mode:
+            _uniform_step(x)  # (a device grid is the caller's contract: include/varpro_hip.h)
         self._keep = (x, Y, w)
         stream = None
         if self.device_mode:
@@ -216,6 +227,8 @@ class BatchProblem:
         self._h = h
         self._have_params = False  # mirrors the handle: set_params / evaluate / fit has run on the current data
         self._keep = None  # the handle owns copies (Y_w = W*Y, t, w)
+        if irf is not None:
+            self.set_irf(irf)
 
     # ---- plumbing ----
     def _as_array(self, a):
@@ -617,6 +630,17 @@ class BatchProblem:
         if self.device_mode and not Y.is_contiguous():
             Y = Y.contiguous()
         check(self.lib.vp_set_observations(self._h, self._ptr(Y)))
+        self._have_params = False
+
+    @_device_entry
+    def set_irf(self, irf):
+        """the instrument response of a model with ``basis.EXP_DECAY_IRF`` / ``basis.IRF`` (vp_set_irf): (m,) shared by the
+        batch or (B, m); the handle copies it (torch tensors: on the device, on the handle's stream).  May be called again
+        to replace the response -- with ``set_observations`` for the next frame; cached results are invalidated."""
+        if not self.irf_kinds:
+            raise ValueError("set_irf: the model has no basis.EXP_DECAY_IRF / basis.IRF function")
+        irf, per_problem = _check_irf(self._as_array(irf), self.B, self.m)
+        check(self.lib.vp_set_irf(self._h, self._ptr(irf), int(per_problem)))
         self._have_params = False
 
     def set_bounds(self, lower, upper):

@@ -39,14 +39,20 @@ enum class Basis : int32_t {
     SinPhase = VP_BASIS_SIN_PHASE,
     Gauss = VP_BASIS_GAUSS,     // peak kinds: the device evaluates their columns into memory (device-column handles)
     Lorentz = VP_BASIS_LORENTZ,
-    Linear = VP_BASIS_LINEAR
+    Linear = VP_BASIS_LINEAR,
+    // IRF reconvolution on a uniform grid (BatchProblem::set_irf): the decay exp(-t/tau) convolved with the instrument
+    // response -- sum_{k<=i} irf_k exp(-(i-k) dt/tau), no factor dt -- and the response itself (the scattered-light term)
+    ExpDecayIrf = VP_BASIS_EXP_DECAY_IRF,
+    Irf = VP_BASIS_IRF
 };
 inline int arity(Basis k) {
     switch (k) {
     case Basis::Const:
-    case Basis::Linear: return 0;
+    case Basis::Linear:
+    case Basis::Irf: return 0;
     case Basis::ExpDecay:
-    case Basis::ExpRate: return 1;
+    case Basis::ExpRate:
+    case Basis::ExpDecayIrf: return 1;
     default: return 2;
     }
 }
@@ -328,6 +334,13 @@ class BatchProblem {
         check(vp_set_bounds(h_, lower.data(), upper.data(), per_problem ? 1 : 0));
     }
     void clear_bounds() { check(vp_set_bounds(h_, nullptr, nullptr, 0)); }
+    // the instrument response of a model with Basis::ExpDecayIrf / Basis::Irf (vp_set_irf): m values shared by the batch or
+    // B*m values; copied by the handle, may be replaced.  Needed before anything that evaluates the model
+    void set_irf(const std::vector<double> &irf) {
+        const bool per_problem = (int64_t)irf.size() == B * m && B > 1;
+        if ((int64_t)irf.size() != m && !per_problem) throw std::invalid_argument("irf must hold m or B*m values");
+        check(vp_set_irf(h_, irf.data(), per_problem ? 1 : 0));
+    }
     // start-point search (vp_search): per problem the best of K candidates by the projected objective; the handle is then
     // in the state of set_params(result.alpha).  candidates: K*q values shared by all problems, or B*K*q with per_problem
     struct SearchResult {

@@ -341,6 +341,11 @@ struct __attribute__((visibility("hidden"))) vp_batch {
     bool bounded = false;
     void *d_lo = nullptr, *d_hi = nullptr; // [q] or [B][q] of the handle's dtype, rounded INTO the box
     int64_t bound_stride = 0;              // 0: one box for all problems, q: per problem
+    // IRF reconvolution kinds (vp_irf.hpp): the instrument response of vp_set_irf, copied into a buffer of the handle
+    bool irf_kinds = false;  // col_model contains VP_BASIS_EXP_DECAY_IRF / VP_BASIS_IRF
+    bool have_irf = false;   // vp_set_irf has been called
+    void *d_irf = nullptr;   // [rows] or [B][rows] of the handle's dtype (sized for the per-problem form at the first call)
+    int64_t irf_stride = 0;  // 0: one response for all problems, rows: per problem
     // batched reverse-communication LM fit of a caller-evaluated model (vp_fit_begin / vp_fit_step_with_basis / vp_fit_end)
     void *d_xf_state = nullptr;      // [B] LM records of the step kernel
     void *d_xf_trial = nullptr;      // [B][q] trial points of the last step
@@ -641,13 +646,21 @@ void fill_cols_params(const vp_batch *h, ColsParams &c) {
     c.t_stride = (h->flags & VP_FLAG_T_PER_PROBLEM) ? h->m : 0;
     c.m = (int)col_rows(h);
     c.B = h->B;
+    c.irf = h->d_irf;
+    c.irf_stride = h->irf_stride;
     c.stream = h->stream;
 }
+// a handle with an IRF kind cannot evaluate a column before vp_set_irf
+#define VP_NEEDS_IRF(h, what)                                                                                          \
+    if ((h)->irf_kinds && !(h)->have_irf)                                                                              \
+    return fail(VP_ERR_INVALID, what ": the model has an IRF reconvolution kind (VP_BASIS_EXP_DECAY_IRF / VP_BASIS_IRF) "  \
+                                     "and the handle has no instrument response yet: call vp_set_irf first")
 // Phi and dPhi of `alpha_dev` [B][q] into the handle's own buffers, which become the columns of the caller-evaluated path.
 // list / count (device): only these problems, `bound` an upper bound of *count; null: all B
 // `internal`: alpha_dev holds the internal parameters of a bounded fit (the bounded column kernel maps them)
 int fill_own_columns(vp_batch *h, const void *alpha_dev, const int32_t *list, const int32_t *count, int64_t bound,
                      const bool internal = false) {
+    VP_NEEDS_IRF(h, "column evaluation");
     const size_t ts = tsize(h->dtype), rows = (size_t)col_rows(h);
     if (int rc = h->ensure(h->col_phi, (size_t)h->B * h->n * rows * ts)) return rc;
     if (h->ext_np > 0)
@@ -1184,6 +1197,23 @@ static int batch_create(vp_batch **out, const vp_model_desc *model, int dtype, i
                         const void *Y, const void *w, double svd_epsilon, int flags, int device, void *hip_stream,
                         const ExtSpec *ext) {
     const bool dev_data = (flags & VP_FLAG_DEVICE_PTRS) != 0;
+    // the IRF reconvolution kinds need a uniform grid; a host grid is checked here (a device grid is the caller's contract)
+    if (model && !ext && t && !dev_data && m > 0 && B > 0 && (dtype == VP_F64 || dtype == VP_F32) && model->n_basis > 0 &&
+        model->n_basis <= VP_MAX_BASIS) {
+        bool irf = false;
+        for (int j = 0; j < model->n_basis; ++j) irf = irf || is_irf_kind(model->kind[j]);
+        const int64_t ngrids = (flags & VP_FLAG_T_PER_PROBLEM) ? B : 1;
+        for (int64_t g = 0; irf && g < ngrids; ++g) {
+            auto at = [&](int64_t i) {
+                return dtype == VP_F64 ? ((const double *)t)[g * m + i] : (double)((const float *)t)[g * m + i];
+            };
+            const double t0 = at(0), dt = m > 1 ? (at(m - 1) - t0) / (double)(m - 1) : 0.0;
+            for (int64_t i = 0; i < m; ++i)
+                if (!(std::fabs(at(i) - t0 - (double)i * dt) <= 1e-6 * std::fabs(dt)) && m > 1)
+                    return fail(VP_ERR_INVALID, "the IRF reconvolution kinds (VP_BASIS_EXP_DECAY_IRF / VP_BASIS_IRF) need a uniform "
+                                                "grid: |t_i - t_0 - i dt| <= 1e-6 |dt| with dt = (t[m-1] - t[0]) / (m-1)");
+        }
+    }
     // (arguments batch_create_impl refuses go to it as they are, for its message)
     if (!out || !model || !Y || (!t && !ext) || m <= 0 || S <= 0 || B <= 0 || (dtype != VP_F64 && dtype != VP_F32) ||
         m >= model->n_basis || model->n_basis > VP_MAX_BASIS)
@@ -1372,7 +1402,8 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
     bool devcols = false;
     if (!ext)
         for (int j = 0; j < model->n_basis; ++j)
-            if (model->kind[j] == VP_BASIS_GAUSS || model->kind[j] == VP_BASIS_LORENTZ || model->kind[j] == VP_BASIS_LINEAR)
+            if (model->kind[j] == VP_BASIS_GAUSS || model->kind[j] == VP_BASIS_LORENTZ || model->kind[j] == VP_BASIS_LINEAR ||
+                is_irf_kind(model->kind[j]))
                 devcols = true;
     if (!ext && (flags & VP_FLAG_DEVICE_COLUMNS)) devcols = true; // ... or any descriptor, on request (the kernel evaluates all kinds)
     vp_model_desc shape_desc;
@@ -1447,6 +1478,8 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
     if (devcols) {
         h->devcols = true;
         h->col_model = *descriptor;
+        for (int j = 0; j < descriptor->n_basis; ++j)
+            if (is_irf_kind(descriptor->kind[j])) h->irf_kinds = true;
     }
     if (int rc = batch_init(h, t, Y, w, hip_stream, data_on_device)) {
         vp_batch_destroy(h);
@@ -1687,6 +1720,7 @@ int vp_fit_end(vp_batch *h, void *alpha_out, void *C_out, vp_report *rep) {
 int vp_set_params(vp_batch *h, const void *alpha) {
     VP_ENTER(h);
     VP_NOT_EXTERNAL(h, "vp_set_params");
+    VP_NEEDS_IRF(h, "vp_set_params");
     if (!alpha) return fail(VP_ERR_INVALID, "null alpha");
     if (int rc = upload_alpha(h, alpha)) return rc;
     if (h->devcols)
@@ -1790,6 +1824,7 @@ int vp_evaluate(vp_batch *h, const void *alpha, void *r_out, void *J_out, void *
                 int32_t *status) {
     VP_ENTER(h);
     VP_NOT_EXTERNAL(h, "vp_evaluate");
+    VP_NEEDS_IRF(h, "vp_evaluate");
     if (!alpha) return fail(VP_ERR_INVALID, "null alpha");
     if (int rc = upload_alpha(h, alpha)) return rc;
     if (h->devcols) {
@@ -1804,6 +1839,7 @@ int vp_evaluate(vp_batch *h, const void *alpha, void *r_out, void *J_out, void *
 int vp_basis(vp_batch *h, const void *alpha, void *Phi_out, void *dPhi_out, int flags) {
     VP_ENTER(h);
     VP_NOT_EXTERNAL(h, "vp_basis");
+    VP_NEEDS_IRF(h, "vp_basis");
     if (!alpha) return fail(VP_ERR_INVALID, "null alpha");
     const size_t ts = tsize(h->dtype);
     if (h->devcols) { // the column kernel straight into the caller's arrays (host-pointer handles: staged)
@@ -1887,6 +1923,7 @@ int devcols_step(vp_batch *h, const bool look, int64_t &n_active) {
 }
 int devcols_fit(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C_out, vp_report *rep) {
     if (!alpha_inout) return fail(VP_ERR_INVALID, "null alpha");
+    VP_NEEDS_IRF(h, "vp_fit");
     if (int rc = xf_begin(h, opts, alpha_inout, 0)) return rc;
     const int64_t limit = 2 * ((int64_t)h->xf_opts.patience * (h->q + 1) + 2);
     Timer tm(h, VP_KERNEL_FIT);
@@ -2081,6 +2118,29 @@ int vp_set_bounds(vp_batch *h, const double *lower, const double *upper, int per
     return VP_ERR_OK;
 }
 
+int vp_set_irf(vp_batch *h, const void *irf, int per_problem) {
+    VP_ENTER(h);
+    if (!h->irf_kinds)
+        return fail(VP_ERR_INVALID, "vp_set_irf: the handle's model has no IRF reconvolution kind (VP_BASIS_EXP_DECAY_IRF / "
+                                    "VP_BASIS_IRF)");
+    if (h->xf_running) return fail(VP_ERR_INVALID, "vp_set_irf during a stepped fit");
+    if (!irf) return fail(VP_ERR_INVALID, "vp_set_irf: null irf");
+    const size_t ts = tsize(h->dtype), rows = (size_t)col_rows(h);
+    // (sized for the per-problem form at the first call: a later call may switch forms)
+    if (int rc = h->ensure(h->d_irf, (size_t)h->B * rows * ts)) return rc;
+    h->have_irf = false; // (until the copy has been enqueued)
+    VP_HIP(hipMemcpyAsync(h->d_irf, irf, (size_t)(per_problem ? h->B : 1) * rows * ts,
+                          device_ptrs(h) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    if (!device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream)); // the caller may reuse its host buffer
+    h->irf_stride = per_problem ? (int64_t)rows : 0;
+    h->have_irf = true;
+    // the cached evaluation / fit and the handle's columns belong to the old response
+    invalidate(h);
+    h->ext_phi = nullptr;
+    h->ext_dphi = nullptr;
+    return VP_ERR_OK;
+}
+
 // ---- start-point search (vp_search.hpp) ---------------------------------------------------------------------------------
 namespace {
 
@@ -2176,6 +2236,7 @@ int vp_search(vp_batch *h, const void *cand, int64_t K, int flags, void *alpha_o
     VP_ENTER(h);
     if (h->xf_running) return fail(VP_ERR_INVALID, "vp_search during a stepped fit");
     VP_NOT_EXTERNAL(h, "vp_search");
+    VP_NEEDS_IRF(h, "vp_search");
     if (h->rhs_allreduce)
         return fail(VP_ERR_UNSUPPORTED, "vp_search: the handle's right-hand sides are sharded over ranks (vp_set_rhs_allreduce)");
     if (!cand) return fail(VP_ERR_INVALID, "null cand");
@@ -2188,7 +2249,8 @@ int vp_search(vp_batch *h, const void *cand, int64_t K, int flags, void *alpha_o
     if (int rc = cd.init(h, cand, (size_t)(per_problem ? h->B : 1) * (size_t)K * h->q * ts)) return rc;
     // from here on the cached evaluation is being replaced
     h->r_valid = false;
-    const bool shared = !per_problem && !(h->flags & (VP_FLAG_T_PER_PROBLEM | VP_FLAG_W_PER_PROBLEM)) && !h->m_user;
+    const bool shared = !per_problem && !(h->flags & (VP_FLAG_T_PER_PROBLEM | VP_FLAG_W_PER_PROBLEM)) && !h->m_user &&
+                        !(h->irf_kinds && h->irf_stride != 0); // (a response per problem: the candidate loop, like a grid per problem)
     {
         SearchClock clk(h);
         if (shared) {
@@ -2607,6 +2669,8 @@ static int kind_arity(int kind) {
     case VP_BASIS_GAUSS:
     case VP_BASIS_LORENTZ: return 2;
     case VP_BASIS_LINEAR: return 0;
+    case VP_BASIS_EXP_DECAY_IRF: return 1;
+    case VP_BASIS_IRF: return 0;
     default: return -1; // (VP_BASIS_EXTERNAL never reaches a descriptor: vp_batch_create_external only)
     }
 }

@@ -4,6 +4,8 @@
 // downstream of the columns is done by the caller-evaluated kernels (vp_ext.hpp, vp_blk_ext.hpp, vp_extfit.hpp, ...) exactly
 // as for a caller's columns.  All eight device kinds are evaluated here, so a descriptor may mix a Gaussian with an
 // exponential tail and a baseline.
+// (The two IRF reconvolution kinds are not pointwise functions of t: their columns come from the scan kernel of vp_irf.hpp,
+// launched behind this one by cols_fill; launch_fill below keeps them out of the descriptor this kernel sees.)
 //
 // Work sharing: a THREAD owns one 16-byte row group (2 fp64 / 4 fp32 rows) of one problem and walks over ALL basis functions
 // there: the exponential / the reciprocal of a basis function is computed once and shared by its value and both derivatives,
@@ -46,9 +48,14 @@ struct ColsParams {
     const int32_t *count;  // device count of the list (read by the kernel)
     const void *lo, *hi;   // both non-null: `alpha` holds INTERNAL parameters u, the bounded kernel maps them; [q] or [B][q]
     int64_t bound_stride;  // 0: one box for all problems, q: per problem
+    const void *irf;       // descriptors with an IRF kind: the response, [m] or [B][irf_stride] (vp_irf.hpp)
+    int64_t irf_stride;    // 0: one response for all problems
     hipStream_t stream;
 };
+// every column of the descriptor: cols_fill_kernel for the pointwise kinds, then the scan kernel for the IRF kinds
 int cols_fill(const ColsParams &p);
+int irf_cols_fill(const ColsParams &p); // the columns of the IRF kinds alone (vp_irf.hpp)
+inline bool is_irf_kind(const int kind) { return kind == VP_BASIS_EXP_DECAY_IRF || kind == VP_BASIS_IRF; }
 // in place on x [B][q] (the handle's dtype): x <- g^-1(x) (to_internal != 0) or x <- g(x), the maps of bound_map / bound_unmap
 int bounds_transform(int dtype, void *x, const void *lo, const void *hi, int64_t bound_stride, int q, int64_t B, int to_internal,
                      hipStream_t stream);
@@ -371,12 +378,13 @@ template <typename T> int launch_fill(const ColsParams &p) {
     if (p.B <= 0 || p.m <= 0 || (!p.phi && !p.dphi)) return VP_ERR_OK;
     ColsArgs<T> a;
     const bool bounded = p.lo && p.hi;
-    a.mdl = p.model;
+    int phi_col[VP_MAX_BASIS], first_pair[VP_MAX_BASIS];
     int ncols = 0, npairs = 0;
     for (int j = 0; j < VP_MAX_BASIS; ++j) {
-        a.phi_col[j] = -1;
+        phi_col[j] = -1;
+        first_pair[j] = npairs;
         if (j >= p.model.n_basis) continue;
-        if (!(p.skip_invariant && p.model.kind[j] == VP_BASIS_CONST)) a.phi_col[j] = ncols++;
+        if (!(p.skip_invariant && p.model.kind[j] == VP_BASIS_CONST)) phi_col[j] = ncols++;
         for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k)
             if (p.model.param[j][k] >= 0) ++npairs;
     }
@@ -385,44 +393,83 @@ template <typename T> int launch_fill(const ColsParams &p) {
     a.t = (const T *)p.t;
     a.alpha = (const T *)p.alpha;
     a.phi = ncols > 0 ? (T *)p.phi : nullptr;
-    a.dphi = npairs > 0 ? (T *)p.dphi : nullptr;
     a.list = p.list;
     a.count = p.count;
     a.t_stride = p.t_stride;
     a.m = p.m;
     a.blocks_per_problem = (p.m + 256 * VW - 1) / (256 * VW);
-    if (!a.phi && !a.dphi) return VP_ERR_OK;
+    if (!a.phi && !(npairs > 0 && p.dphi)) return VP_ERR_OK;
     // 16-byte groups need m to be a multiple of the group and every array (each column starts a multiple of m from its base)
     // 16-byte aligned
     auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     const bool vec = p.m % VW == 0 && al16(p.t) && al16(p.phi) && al16(p.dphi) && (p.t_stride % VW) == 0;
     const int64_t per_launch = ((int64_t)0x7fffffff / a.blocks_per_problem); // problems one grid can cover
-    for (int64_t first = 0; first < p.B; first += per_launch) {
-        const int64_t nb = p.B - first < per_launch ? p.B - first : per_launch;
-        a.first = first;
-        const dim3 grid((unsigned)(nb * a.blocks_per_problem)), block(256);
-        if (bounded) {
-            ColsBoundArgs<T> ba;
-            static_cast<ColsArgs<T> &>(ba) = a;
-            ba.lo = (const T *)p.lo;
-            ba.hi = (const T *)p.hi;
-            ba.bound_stride = p.bound_stride;
-            if (vec) {
-                if (p.nt) hipLaunchKernelGGL((cols_fill_bounded_kernel<T, true, true>), grid, block, 0, p.stream, ba);
-                else hipLaunchKernelGGL((cols_fill_bounded_kernel<T, true, false>), grid, block, 0, p.stream, ba);
+    // one launch over the functions a.mdl lists, its derivative columns from pair `pair0` of the problem on
+    auto launch = [&](const int pair0) -> int {
+        a.dphi = npairs > 0 && p.dphi ? (T *)p.dphi + (int64_t)pair0 * p.m : nullptr;
+        if (!a.phi && !a.dphi) return VP_ERR_OK;
+        for (int64_t first = 0; first < p.B; first += per_launch) {
+            const int64_t nb = p.B - first < per_launch ? p.B - first : per_launch;
+            a.first = first;
+            const dim3 grid((unsigned)(nb * a.blocks_per_problem)), block(256);
+            if (bounded) {
+                ColsBoundArgs<T> ba;
+                static_cast<ColsArgs<T> &>(ba) = a;
+                ba.lo = (const T *)p.lo;
+                ba.hi = (const T *)p.hi;
+                ba.bound_stride = p.bound_stride;
+                if (vec) {
+                    if (p.nt) hipLaunchKernelGGL((cols_fill_bounded_kernel<T, true, true>), grid, block, 0, p.stream, ba);
+                    else hipLaunchKernelGGL((cols_fill_bounded_kernel<T, true, false>), grid, block, 0, p.stream, ba);
+                } else {
+                    if (p.nt) hipLaunchKernelGGL((cols_fill_bounded_kernel<T, false, true>), grid, block, 0, p.stream, ba);
+                    else hipLaunchKernelGGL((cols_fill_bounded_kernel<T, false, false>), grid, block, 0, p.stream, ba);
+                }
+            } else if (vec) {
+                if (p.nt) hipLaunchKernelGGL((cols_fill_kernel<T, true, true>), grid, block, 0, p.stream, a);
+                else hipLaunchKernelGGL((cols_fill_kernel<T, true, false>), grid, block, 0, p.stream, a);
             } else {
-                if (p.nt) hipLaunchKernelGGL((cols_fill_bounded_kernel<T, false, true>), grid, block, 0, p.stream, ba);
-                else hipLaunchKernelGGL((cols_fill_bounded_kernel<T, false, false>), grid, block, 0, p.stream, ba);
+                if (p.nt) hipLaunchKernelGGL((cols_fill_kernel<T, false, true>), grid, block, 0, p.stream, a);
+                else hipLaunchKernelGGL((cols_fill_kernel<T, false, false>), grid, block, 0, p.stream, a);
             }
-        } else if (vec) {
-            if (p.nt) hipLaunchKernelGGL((cols_fill_kernel<T, true, true>), grid, block, 0, p.stream, a);
-            else hipLaunchKernelGGL((cols_fill_kernel<T, true, false>), grid, block, 0, p.stream, a);
-        } else {
-            if (p.nt) hipLaunchKernelGGL((cols_fill_kernel<T, false, true>), grid, block, 0, p.stream, a);
-            else hipLaunchKernelGGL((cols_fill_kernel<T, false, false>), grid, block, 0, p.stream, a);
+            if (hipGetLastError() != hipSuccess) return VP_ERR_HIP;
         }
-        if (hipGetLastError() != hipSuccess) return VP_ERR_HIP;
+        return VP_ERR_OK;
+    };
+    // The kernel numbers its derivative columns by counting the parameters of the functions it walks, so the functions of
+    // the IRF kinds -- whose columns come from the scan kernel (vp_irf.hpp) -- are taken out of the descriptor it sees: a
+    // VP_BASIS_IRF simply (it has no parameters), and at every VP_BASIS_EXP_DECAY_IRF the descriptor is cut, the run of
+    // functions behind it going to a launch of its own whose dPhi starts at that run's first pair.  A descriptor without
+    // these kinds is one run: the launch it always was.
+    a.mdl = p.model;
+    int run = 0, run_pair0 = 0;
+    bool stores = false; // the run has a column to write
+    auto flush = [&]() -> int {
+        int rc = VP_ERR_OK;
+        if (run > 0 && stores) {
+            a.mdl.n_basis = run;
+            for (int j = run; j < VP_MAX_BASIS; ++j) a.phi_col[j] = -1;
+            rc = launch(run_pair0);
+        }
+        run = 0;
+        stores = false;
+        return rc;
+    };
+    for (int j = 0; j < p.model.n_basis; ++j) {
+        const int kind = p.model.kind[j];
+        if (kind == VP_BASIS_IRF) continue;
+        if (kind == VP_BASIS_EXP_DECAY_IRF) {
+            if (int rc = flush()) return rc;
+            continue;
+        }
+        if (run == 0) run_pair0 = first_pair[j];
+        a.mdl.kind[run] = kind;
+        for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k) a.mdl.param[run][k] = p.model.param[j][k];
+        a.phi_col[run] = phi_col[j];
+        if ((a.phi && phi_col[j] >= 0) || (p.dphi && (p.model.param[j][0] >= 0 || p.model.param[j][1] >= 0))) stores = true;
+        ++run;
     }
+    if (int rc = flush()) return rc;
     return VP_ERR_OK;
 }
 

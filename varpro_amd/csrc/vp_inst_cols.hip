@@ -7,7 +7,10 @@
 namespace vp {
 
 int cols_fill(const ColsParams &p) {
-    return p.dtype == VP_F64 ? cols::launch_fill<double>(p) : cols::launch_fill<float>(p);
+    if (int rc = p.dtype == VP_F64 ? cols::launch_fill<double>(p) : cols::launch_fill<float>(p)) return rc;
+    for (int j = 0; j < p.model.n_basis; ++j)
+        if (is_irf_kind(p.model.kind[j])) return irf_cols_fill(p); // (their columns: the scan kernel, vp_inst_irf.hip)
+    return VP_ERR_OK;
 }
 
 int bounds_transform(int dtype, void *x, const void *lo, const void *hi, int64_t bound_stride, int q, int64_t B, int to_internal,

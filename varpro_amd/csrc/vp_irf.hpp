@@ -1,0 +1,240 @@
+// vp_irf.hpp -- the columns of the IRF reconvolution kinds (VP_BASIS_EXP_DECAY_IRF, VP_BASIS_IRF) of device-column handles.
+//
+// A reconvolved exponential is not a pointwise function of t: on a uniform grid of step dt, with rho = exp(-dt/tau),
+//   Phi_i        = sum_{k<=i} irf_k rho^(i-k)              F_i = irf_i + rho F_{i-1},        F_{-1} = 0
+//   dPhi_i/dtau  = dt/tau^2 H_i,  H_i = sum_k (i-k) rho^(i-k) irf_k     H_i = rho (H_{i-1} + F_{i-1})
+// (rectangle rule: lag 0 included, no factor dt -- the linear coefficient absorbs it).  cols_fill_kernel gives a thread a row
+// group and cannot compute this; the kernel here is a scan of that two-state linear recurrence and fills ONLY the columns of
+// the two IRF kinds -- the other functions of the descriptor still come from cols_fill_kernel (vp_cols.hpp launch_fill),
+// which leaves these columns alone.
+//
+// Work sharing: ONE WAVEFRONT walks one (problem, IRF-kind function) in tiles of 64 row groups (128 fp64 / 256 fp32 rows).
+// A lane owns the 16-byte group cols_fill_kernel's thread owns, so an IRF load and a column store are 1 KB contiguous per wave
+// instruction (element-wise where m is not a multiple of the group or an array is not 16-byte aligned).  Per tile
+//   1. every lane runs the recurrence over its own rows from a zero start: the affine map of s rows is
+//        (F, H) -> (rho^s F + F_loc, rho^s (H + s F) + H_loc)                     -- all lanes share rho
+//   2. four DPP row_shr steps compose the lanes' maps inside each 16-lane row (factors rho^VW, ^2VW, ^4VW, ^8VW by repeated
+//      squaring), v_readlane takes the four row totals and three wave-uniform compositions (factor rho^16VW) chain them behind
+//      the carry of the previous tile -- no LDS, no barrier
+//   3. a lane's incoming state is its row's prefix advanced by ITS factor exp(-(k VW dt)/tau), k = lane % 16 -- formed once
+//      per function with the library's exp -- plus the exclusive in-row scan; from there it runs the recurrence over its
+//      rows once more and stores them.  Lane 63's last row is the next tile's carry (it stays in registers).
+// The function, tau and everything derived from them are wave-uniform (SGPRs / uniform VALU).  A problem's tiles run serially
+// on its wave: rows are not split over several waves.
+//
+// Honoured as in cols_fill: the index list of a stepped fit, skip_invariant (through the column numbering), phi / dphi ==
+// nullptr, per-problem grids (dt_b = (t_b[m-1] - t_b[0])/(m-1); m == 1: dt = 0), both dtypes, and the bounded form: tau = g(u)
+// through bound_map, the derivative column multiplied by dtau/du.  tau <= 0 or NaN gives NaN columns (latched per problem
+// downstream); a non-finite IRF entry makes every later row non-finite.
+#pragma once
+#include "vp_cols.hpp"
+#include "vp_device.hpp"
+
+namespace vp {
+namespace cols {
+
+template <typename T> struct IrfArgs {
+    const T *t, *alpha, *irf;
+    T *phi, *dphi;
+    const T *lo, *hi; // the bounded kernel only: `alpha` holds internal parameters
+    const int32_t *list, *count;
+    int64_t t_stride, irf_stride, bound_stride, first, slots; // slots: problems (or list slots) this launch covers
+    int m, q, n_phi_cols, n_pairs, nf;                        // nf: functions of the IRF kinds that have something to store
+    int kind[VP_MAX_BASIS], phi_col[VP_MAX_BASIS], pair[VP_MAX_BASIS], param[VP_MAX_BASIS];
+};
+
+constexpr int DPP_ROW_SHR = 0x110; // + distance 1..15: lane k of a 16-lane row reads lane k - d, lanes k < d read 0
+
+// the IRF group of lane-row i (zeros beyond m)
+template <typename T, bool VEC>
+__device__ __forceinline__ void load_group(const T *__restrict__ src, const int i, const int m, T (&x)[Vec<T>::VW]) {
+    constexpr int VW = Vec<T>::VW;
+    if constexpr (VEC) {
+        typename Vec<T>::type v;
+#pragma unroll
+        for (int e = 0; e < VW; ++e) v[e] = T(0);
+        if (i < m) v = *reinterpret_cast<const typename Vec<T>::type *>(src + i);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) x[e] = v[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e) x[e] = i + e < m ? src[i + e] : T(0);
+    }
+}
+
+template <typename T, bool VEC, bool NT, bool BND> __global__ void __launch_bounds__(256) irf_cols_kernel(const IrfArgs<T> a) {
+    constexpr int VW = Vec<T>::VW, TILE = 64 * VW;
+    const int lane = (int)(threadIdx.x & 63u);
+    const unsigned wave = blockIdx.x * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned nf = (unsigned)a.nf;
+    const unsigned slot_local = wave / nf;
+    const int f = (int)(wave - slot_local * nf);
+    if ((int64_t)slot_local >= a.slots) return;
+    int64_t b = a.first + (int64_t)slot_local;
+    if (a.list) {
+        if (b >= (int64_t)*a.count) return;
+        b = a.list[b];
+    }
+    const int m = a.m;
+    const T *irf = a.irf + b * a.irf_stride;
+    T *phi = (a.phi && a.phi_col[f] >= 0) ? a.phi + (b * (int64_t)a.n_phi_cols + a.phi_col[f]) * m : nullptr;
+    if (a.kind[f] == VP_BASIS_IRF) { // the response itself: a copy
+        if (!phi) return;
+        for (int base = 0; base < m; base += TILE) {
+            const int i = base + VW * lane;
+            T x[VW];
+            load_group<T, VEC>(irf, i, m, x);
+            if (i < m) store_group<T, VEC, NT>(phi, i, m, x);
+        }
+        return;
+    }
+    T *dphi = a.dphi ? a.dphi + (b * (int64_t)a.n_pairs + a.pair[f]) * m : nullptr;
+    // ---- what the function's rows share (wave-uniform) ----
+    const int pi = a.param[f];
+    T tau = a.alpha[b * a.q + pi], dtau_du = T(1);
+    if constexpr (BND) bound_map<T>(tau, a.lo[b * a.bound_stride + pi], a.hi[b * a.bound_stride + pi], tau, dtau_du);
+    if (!(tau > T(0))) tau = T(0) / T(0); // tau <= 0, NaN: not a decay -- NaN columns
+    const T *tg = a.t + b * a.t_stride;
+    const T dt = m > 1 ? (tg[m - 1] - tg[0]) / T(m - 1) : T(0);
+    const T rho = cexp(-(dt / tau)); // (tau -> 0+: exp(-inf) = 0, the column is the response)
+    const T dscale = (dt / (tau * tau)) * dtau_du;
+    // rho^(VW d), d = 1, 2, 4, 8, 16 lanes
+    T pw[5];
+    pw[0] = rho * rho;
+    if constexpr (VW == 4) pw[0] *= pw[0];
+#pragma unroll
+    for (int s = 1; s < 5; ++s) pw[s] = pw[s - 1] * pw[s - 1];
+    // the lane's own factor: k groups behind the first lane of its 16-lane row
+    const int k = lane & 15, row = lane >> 4;
+    const T kspan = T(VW * k);
+    const T lf = k == 0 ? T(1) : cexp(-((kspan * dt) / tau));
+    T cF = T(0), cH = T(0); // state at the end of the previous tile (uniform)
+    T xn[VW];
+    load_group<T, VEC>(irf, VW * lane, m, xn);
+    for (int base = 0; base < m; base += TILE) {
+        const int i = base + VW * lane;
+        T x[VW];
+#pragma unroll
+        for (int e = 0; e < VW; ++e) x[e] = xn[e];
+        if (base + TILE < m) load_group<T, VEC>(irf, i + TILE, m, xn); // (the next tile's group, in flight during the scan)
+        // 1. the lane's rows from a zero start
+        T F = T(0), H = T(0);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+            H = rho * (H + F);
+            F = tfma(rho, F, x[e]);
+        }
+        // 2. inclusive scan inside the 16-lane rows, then the rows behind the carry
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            T Fl, Hl;
+            if (s == 0) Fl = dpp<DPP_ROW_SHR + 1>(F), Hl = dpp<DPP_ROW_SHR + 1>(H);
+            else if (s == 1) Fl = dpp<DPP_ROW_SHR + 2>(F), Hl = dpp<DPP_ROW_SHR + 2>(H);
+            else if (s == 2) Fl = dpp<DPP_ROW_SHR + 4>(F), Hl = dpp<DPP_ROW_SHR + 4>(H);
+            else Fl = dpp<DPP_ROW_SHR + 8>(F), Hl = dpp<DPP_ROW_SHR + 8>(H);
+            H = tfma(pw[s], tfma(T(VW << s), Fl, Hl), H);
+            F = tfma(pw[s], Fl, F);
+        }
+        T pF = cF, pH = cH; // prefix of this lane's row
+        {
+            T qF = cF, qH = cH;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const T rF = readlane(F, 16 * r + 15), rH = readlane(H, 16 * r + 15);
+                qH = tfma(pw[4], tfma(T(16 * VW), qF, qH), rH);
+                qF = tfma(pw[4], qF, rF);
+                if (row > r) pF = qF, pH = qH;
+            }
+        }
+        // 3. the lane's incoming state, its rows, the carry
+        F = tfma(lf, pF, dpp<DPP_ROW_SHR + 1>(F));
+        H = tfma(lf, tfma(kspan, pF, pH), dpp<DPP_ROW_SHR + 1>(H));
+        T fo[VW], ho[VW];
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+            H = rho * (H + F);
+            F = tfma(rho, F, x[e]);
+            fo[e] = F;
+            ho[e] = dscale * H;
+        }
+        if (i < m) {
+            if (phi) store_group<T, VEC, NT>(phi, i, m, fo);
+            if (dphi) store_group<T, VEC, NT>(dphi, i, m, ho);
+        }
+        cF = readlane(F, 63);
+        cH = readlane(H, 63);
+    }
+}
+
+template <typename T> int launch_irf(const ColsParams &p) {
+    constexpr int VW = Vec<T>::VW;
+    if (p.B <= 0 || p.m <= 0 || (!p.phi && !p.dphi)) return VP_ERR_OK;
+    if (!p.irf) return VP_ERR_INVALID;
+    IrfArgs<T> a;
+    const bool bounded = p.lo && p.hi;
+    int ncols = 0, npairs = 0, nf = 0;
+    for (int j = 0; j < p.model.n_basis && j < VP_MAX_BASIS; ++j) {
+        const int kind = p.model.kind[j];
+        const int col = (p.skip_invariant && kind == VP_BASIS_CONST) ? -1 : ncols++;
+        const bool wanted = kind == VP_BASIS_IRF ? p.phi != nullptr : kind == VP_BASIS_EXP_DECAY_IRF;
+        if (wanted) {
+            a.kind[nf] = kind;
+            a.phi_col[nf] = col;
+            a.pair[nf] = npairs;
+            a.param[nf] = p.model.param[j][0];
+            ++nf;
+        }
+        for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k)
+            if (p.model.param[j][k] >= 0) ++npairs;
+    }
+    if (nf == 0) return VP_ERR_OK;
+    for (int f = nf; f < VP_MAX_BASIS; ++f) a.kind[f] = a.phi_col[f] = a.pair[f] = a.param[f] = 0;
+    a.t = (const T *)p.t;
+    a.alpha = (const T *)p.alpha;
+    a.irf = (const T *)p.irf;
+    a.phi = (T *)p.phi;
+    a.dphi = npairs > 0 ? (T *)p.dphi : nullptr;
+    a.lo = (const T *)p.lo;
+    a.hi = (const T *)p.hi;
+    a.list = p.list;
+    a.count = p.count;
+    a.t_stride = p.t_stride;
+    a.irf_stride = p.irf_stride;
+    a.bound_stride = p.bound_stride;
+    a.m = p.m;
+    a.q = p.model.n_params;
+    a.n_phi_cols = ncols;
+    a.n_pairs = npairs;
+    a.nf = nf;
+    auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    const bool vec = p.m % VW == 0 && al16(p.irf) && al16(p.phi) && al16(p.dphi) && (p.irf_stride % VW) == 0;
+    const int64_t per_launch = (int64_t)0x7fffffff / nf; // problems one grid can cover (4 waves per workgroup)
+    for (int64_t first = 0; first < p.B; first += per_launch) {
+        const int64_t nb = p.B - first < per_launch ? p.B - first : per_launch;
+        a.first = first;
+        a.slots = nb;
+        const dim3 grid((unsigned)((nb * nf + 3) / 4)), block(256);
+#define VP_IRF_LAUNCH(V, N, BD) hipLaunchKernelGGL((irf_cols_kernel<T, V, N, BD>), grid, block, 0, p.stream, a)
+        if (bounded) {
+            if (vec) {
+                if (p.nt) VP_IRF_LAUNCH(true, true, true);
+                else VP_IRF_LAUNCH(true, false, true);
+            } else {
+                if (p.nt) VP_IRF_LAUNCH(false, true, true);
+                else VP_IRF_LAUNCH(false, false, true);
+            }
+        } else if (vec) {
+            if (p.nt) VP_IRF_LAUNCH(true, true, false);
+            else VP_IRF_LAUNCH(true, false, false);
+        } else {
+            if (p.nt) VP_IRF_LAUNCH(false, true, false);
+            else VP_IRF_LAUNCH(false, false, false);
+        }
+#undef VP_IRF_LAUNCH
+        if (hipGetLastError() != hipSuccess) return VP_ERR_HIP;
+    }
+    return VP_ERR_OK;
+}
+
+} // namespace cols
+} // namespace vp

@@ -28,15 +28,70 @@ class basis:
     GAUSS = 6       # exp(-(t - p0)^2 / (2 p1^2))     peak at p0, standard deviation p1
     LORENTZ = 7     # p1^2 / ((t - p0)^2 + p1^2)      peak at p0, half width at half maximum p1
     LINEAR = 8      # t                     (invariant_function: a sloped baseline)
-    ARITY = {CONST: 0, EXP_DECAY: 1, EXP_RATE: 1, EXP_COS: 2, SIN_PHASE: 2, GAUSS: 2, LORENTZ: 2, LINEAR: 0}
+    # IRF reconvolution on a UNIFORM grid of step dt, rho = exp(-dt/p0); irf: the instrument response of the problem
+    # (BatchProblem(..., irf=) / set_irf, SeparableProblemBuilder.instrument_response).  Rectangle rule: lag 0 included, no dt
+    EXP_DECAY_IRF = 9   # sum_{k<=i} irf_k rho^(i-k)      the decay exp(-t/p0) convolved with the response
+    IRF = 10            # irf_i                 (invariant_function: the scattered-light term)
+    ARITY = {CONST: 0, EXP_DECAY: 1, EXP_RATE: 1, EXP_COS: 2, SIN_PHASE: 2, GAUSS: 2, LORENTZ: 2, LINEAR: 0,
+             EXP_DECAY_IRF: 1, IRF: 0}
     NAME = {CONST: "const", EXP_DECAY: "exp_decay", EXP_RATE: "exp_rate", EXP_COS: "exp_cos", SIN_PHASE: "sin_phase",
-            GAUSS: "gauss", LORENTZ: "lorentz", LINEAR: "linear"}
+            GAUSS: "gauss", LORENTZ: "lorentz", LINEAR: "linear", EXP_DECAY_IRF: "exp_decay_irf", IRF: "irf"}
+    # kinds that need the instrument response
+    IRF_KINDS = (EXP_DECAY_IRF, IRF)
     # kinds whose columns the device evaluates into memory (a device-column handle, include/varpro_hip.h)
-    DEVICE_COLUMN = (GAUSS, LORENTZ, LINEAR)
+    DEVICE_COLUMN = (GAUSS, LORENTZ, LINEAR, EXP_DECAY_IRF, IRF)
 
 
-def _kind_columns(kind, x, p0, p1):
+def uniform_step(x, what="grid"):
+    """dt = (x[-1] - x[0]) / (m - 1) of a grid the IRF kinds accept (last axis; m == 1: 0), ValueError where
+    |x_i - x_0 - i dt| > 1e-6 |dt| (include/varpro_hip.h, "IRF reconvolution")"""
+    x = np.asarray(x, dtype=np.float64)
+    m = x.shape[-1]
+    if m == 1:
+        return np.zeros(x.shape[:-1])
+    dt = (x[..., -1] - x[..., 0]) / (m - 1)
+    dev = np.abs(x - x[..., :1] - np.arange(m) * dt[..., None])
+    if not np.all(dev <= 1e-6 * np.abs(dt)[..., None]):
+        raise ValueError("NonUniformGrid: the IRF reconvolution kinds need a uniform %s: |x_i - x_0 - i dt| <= 1e-6 |dt|" % what)
+    return dt
+
+
+def check_irf(irf, B, m):
+    """(irf, per_problem) for a batch of B problems of m samples: shape (m,) shared or (B, m); ValueError otherwise"""
+    shape = tuple(int(s) for s in irf.shape)
+    if shape == (m,):
+        return irf, False
+    if shape == (B, m):
+        return irf, True
+    raise ValueError("InvalidLengthOfIrf: the instrument response must have shape (%d,) or (%d, %d), got %r" % (m, B, m, shape))
+
+
+def irf_columns(irf, dt, tau):
+    """numpy mirror of the scan kernel (vp_irf.hpp), the plain sequential recurrence in the dtype of irf:
+    F_i = irf_i + rho F_{i-1}, H_i = rho (H_{i-1} + F_{i-1}), rho = exp(-dt/tau) -> (F, dt/tau^2 H)"""
+    irf = np.asarray(irf)
+    T = irf.dtype.type
+    dt, tau = T(dt), T(tau)
+    F, H = np.empty_like(irf), np.empty_like(irf)
+    with np.errstate(all="ignore"):
+        rho = np.exp(-(dt / tau)) if tau > 0 else T(np.nan)
+        f = h = T(0)
+        for i in range(irf.size):
+            h = rho * (h + f)
+            f = irf[i] + rho * f
+            F[i], H[i] = f, h
+        return F, (dt / (tau * tau)) * H
+
+
+def _kind_columns(kind, x, p0, p1, irf=None):
     """numpy mirror of one basis kind: (f, [df/dp0, df/dp1][:arity]) on the grid x (include/varpro_hip.h)"""
+    if kind in basis.IRF_KINDS:
+        if irf is None:
+            raise ModelError("the model has an IRF reconvolution kind and no instrument response (model.irf)")
+        if kind == basis.IRF:
+            return np.array(irf, dtype=x.dtype), []
+        f, d = irf_columns(np.asarray(irf, dtype=x.dtype), uniform_step(x), p0)
+        return f, [d]
     if kind == basis.CONST:
         return np.ones_like(x), []
     if kind == basis.LINEAR:
@@ -93,6 +148,7 @@ class SeparableModel:
             raise TypeError("ScalarType must be float64 or float32")
         self.x = np.ascontiguousarray(x, dtype=self.dtype).reshape(-1)
         self._alpha = np.ascontiguousarray(initial_parameters, dtype=self.dtype).reshape(-1)
+        self.irf = None  # IRF kinds: the response of the single-problem surface (SeparableProblemBuilder.instrument_response)
         # dependency pairs in model order (basis-major): the layout of vp_basis' dPhi output
         self.pairs = [(j, a, pi) for j, ps in enumerate(self.param_indices) for a, pi in enumerate(ps)]
 
@@ -139,7 +195,7 @@ class SeparableModel:
         with np.errstate(all="ignore"):
             for j, (kind, ps) in enumerate(zip(self.kinds, self.param_indices)):
                 args = [a[pi] for pi in ps] + [None, None]
-                f, ds = _kind_columns(kind, x, args[0], args[1])
+                f, ds = _kind_columns(kind, x, args[0], args[1], self.irf)
                 phi[0, j] = f
                 for d in ds:
                     dphi[0, pair] = d
@@ -396,6 +452,11 @@ class SeparableModelBuilder:
                                       "use it." % n)
         if self._x is None:
             raise ModelBuildError("MissingX", "Missing vector for independent variable x")
+        if any(f["kind"] in basis.IRF_KINDS for f in self._functions):
+            try:
+                uniform_step(np.asarray(self._x).reshape(-1), "independent variable")
+            except ValueError as e:
+                raise ModelBuildError("NonUniformGrid", str(e))
         if self._initial is None:
             raise ModelBuildError("MissingInitialParameters", "Missing initial guesses for model parameters")
         if len(self._functions) > _lib.VP_MAX_BASIS or len(self._names) > _lib.VP_MAX_PARAMS:

@@ -19,9 +19,10 @@ except Exception:  # pragma: no cover
 
 class FitPipeline:
     def __init__(self, model, first_batch, x=None, weights=None, epsilon=None, n_slots=2, lower=None, upper=None,
-                 device_columns=False):
+                 device_columns=False, irf=None):
         """first_batch: a torch CUDA tensor (B, m) or (B, S, m) that fixes the batch shape and the device;
-        lower / upper: box bounds of every fit (BatchProblem.set_bounds), set on each slot's handle"""
+        lower / upper: box bounds of every fit (BatchProblem.set_bounds), set on each slot's handle;
+        irf: the instrument response of a model with an IRF kind (BatchProblem.set_irf), copied into each slot's handle"""
         if torch is None or not isinstance(first_batch, torch.Tensor) or not first_batch.is_cuda:
             raise ValueError("FitPipeline works on torch CUDA tensors (device-pointer mode)")
         self.device = first_batch.device
@@ -31,7 +32,7 @@ class FitPipeline:
             st.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(st):
                 self.slots.append(BatchProblem(model, first_batch, x=x, weights=weights, epsilon=epsilon,
-                                               device_columns=device_columns))
+                                               device_columns=device_columns, irf=irf))
         self._k = 0
         if lower is not None or upper is not None:
             self.set_bounds(lower, upper)
@@ -41,6 +42,17 @@ class FitPipeline:
         it waits for each slot's stream)"""
         for h in self.slots:
             h.set_bounds(lower, upper)
+
+    def set_irf(self, irf):
+        """the instrument response of the fits submitted from now on (BatchProblem.set_irf on every slot, each copy on its
+        slot's stream after the current stream's work)"""
+        cur = torch.cuda.current_stream(self.device)
+        for h, st in zip(self.slots, self.streams):
+            st.wait_stream(cur)
+            if isinstance(irf, torch.Tensor) and irf.is_cuda:
+                irf.record_stream(st)
+            with torch.cuda.stream(st):
+                h.set_irf(irf)
 
     def submit(self, Y, alpha0, solver=None, want_coefficients=True):
         """enqueue the fit of one batch (asynchronous); returns (alpha, C, report, slot_index).  Y and alpha0 must be

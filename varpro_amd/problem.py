@@ -10,6 +10,7 @@ src/problem.rs:57-212 (problem state and accessors), src/solvers/levmar/mod.rs:2
 import numpy as np
 
 from .batch import BatchProblem, STATUS_OK
+from .model import basis
 
 
 class SeparableProblemBuilderError(ValueError):
@@ -23,12 +24,12 @@ class SeparableProblemBuilderError(ValueError):
 class SeparableProblem:
     """One separable least-squares problem living on the GPU (B = 1 batch handle)."""
 
-    def __init__(self, model, Y, weights, epsilon, mrhs):
+    def __init__(self, model, Y, weights, epsilon, mrhs, irf=None):
         self._model = model
         self._mrhs = mrhs
         self._weights = weights
         Yb = Y.T[None, :, :] if mrhs else Y[None, :]  # (1, S, m) / (1, m)
-        self._batch = BatchProblem(model, np.ascontiguousarray(Yb), x=model.x, weights=weights, epsilon=epsilon)
+        self._batch = BatchProblem(model, np.ascontiguousarray(Yb), x=model.x, weights=weights, epsilon=epsilon, irf=irf)
         self.m, self.S, self.n, self.q = self._batch.m, self._batch.S, self._batch.n, self._batch.q
         # build(): initial set_params with the model's current parameters (src/problem/builder.rs:321)
         self.set_params(model.params())
@@ -86,6 +87,7 @@ class SeparableProblemBuilder:
         self._Y = None
         self._weights = None
         self._epsilon = None
+        self._irf = None
 
     @classmethod
     def new(cls, model):
@@ -101,6 +103,11 @@ class SeparableProblemBuilder:
 
     def weights(self, w):
         self._weights = np.asarray(w, dtype=self._model.dtype).reshape(-1)
+        return self
+
+    def instrument_response(self, irf):
+        """the instrument response of a model with ``basis.EXP_DECAY_IRF`` / ``basis.IRF``: one value per sample"""
+        self._irf = np.asarray(irf, dtype=self._model.dtype)
         return self
 
     def epsilon(self, eps):
@@ -126,4 +133,16 @@ class SeparableProblemBuilder:
         if self._weights is not None and self._weights.size != Y.shape[0]:
             raise SeparableProblemBuilderError("InvalidLengthOfWeights",
                                                "The weights must have the same length as the data y.")
-        return SeparableProblem(self._model, Y, self._weights, self._epsilon, self._mrhs)
+        needs_irf = any(k in basis.IRF_KINDS for k in self._model.kinds)
+        if self._irf is not None and not needs_irf:
+            raise SeparableProblemBuilderError("UnexpectedIrf", "the model has no basis.EXP_DECAY_IRF / basis.IRF function")
+        if needs_irf:
+            if self._irf is None:
+                raise SeparableProblemBuilderError("IrfMissing", "the model has an IRF reconvolution kind: "
+                                                   "instrument_response(irf) not provided")
+            if self._irf.ndim != 1 or self._irf.size != x_len:
+                raise SeparableProblemBuilderError(
+                    "InvalidLengthOfIrf", "The instrument response must be a vector of the length of x (%d), got shape %r"
+                    % (x_len, tuple(self._irf.shape)))
+            self._model.irf = self._irf.copy()  # (the model surface -- eval / eval_partial_deriv -- mirrors it on the host)
+        return SeparableProblem(self._model, Y, self._weights, self._epsilon, self._mrhs, self._irf)
