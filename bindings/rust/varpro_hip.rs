@@ -55,6 +55,8 @@ pub const VP_BASIS_LINEAR: i32 = 8;
 pub const VP_BASIS_EXP_DECAY_IRF: i32 = 9;
 /// the instrument response itself (no parameters): the scattered-light term
 pub const VP_BASIS_IRF: i32 = 10;
+/// the periodic form of kind 9: the response repeats every period `T >= m dt` (`vp_set_irf_period`; default `T = m dt`)
+pub const VP_BASIS_EXP_DECAY_IRF_PERIODIC: i32 = 11;
 pub const VP_F64: i32 = 0;
 pub const VP_FLAG_OWN_STREAM: i32 = 8;
 pub const VP_FLAG_NO_GRID_RECURRENCE: i32 = 16;
@@ -81,6 +83,8 @@ extern "C" {
     /// instrument response of a handle whose descriptor has an IRF kind: `[m]` or `[B][m]` in the handle's dtype and address
     /// space, copied by the handle; may be called again to replace it
     pub fn vp_set_irf(h: *mut vp_batch, irf: *const c_void, per_problem: i32) -> i32;
+    /// period of `VP_BASIS_EXP_DECAY_IRF_PERIODIC` in grid units, shared by the batch; 0 (the default): the record is one period
+    pub fn vp_set_irf_period(h: *mut vp_batch, period: f64) -> i32;
     /// start-point search: per problem the best of `k` candidates (`[K][q]`, or `[B][K][q]` with `VP_SEARCH_PER_PROBLEM`) by
     /// the projected objective; leaves the handle in the state of `vp_set_params(h, alpha_out)`.  Outputs may be null.
     pub fn vp_search(h: *mut vp_batch, cand: *const c_void, k: i64, flags: i32, alpha_out: *mut c_void,

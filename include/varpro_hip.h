@@ -77,7 +77,10 @@ enum {
      * grid of step dt, rho = exp(-dt/p0).  Rectangle rule: lag 0 included, NO factor dt (the linear coefficient absorbs it) */
     VP_BASIS_EXP_DECAY_IRF = 9, /* sum_{k<=i} irf_k rho^(i-k)     d/dp0 = dt/p0^2 sum_{k<=i} (i-k) rho^(i-k) irf_k
                                    i.e. F_i = irf_i + rho F_{i-1}, H_i = rho (H_{i-1} + F_{i-1}), d/dp0 = dt/p0^2 H_i      */
-    VP_BASIS_IRF = 10           /* irf_i                   invariant (no parameters): the scattered-light term             */
+    VP_BASIS_IRF = 10,          /* irf_i                   invariant (no parameters): the scattered-light term             */
+    /* kind 9 with the response repeating every period T = P dt, P >= m real (see "Periodic IRF reconvolution" below):
+     * sum_{p>=0} sum_k irf_k rho^(i-k+pP) over the terms with i-k+pP >= 0; the same recurrence from a non-zero start   */
+    VP_BASIS_EXP_DECAY_IRF_PERIODIC = 11
 };
 
 /*
@@ -131,6 +134,24 @@ enum {
  * two end points only.  tau <= 0, a NaN tau or a non-finite response entry give non-finite columns, latched per problem
  * like every other non-finite Phi.  Bounds, vp_search and the statistics work as on any device-column handle (a response
  * per problem sends vp_search down its candidate loop, like a grid per problem).
+ *
+ * Periodic IRF reconvolution.  VP_BASIS_EXP_DECAY_IRF assumes the decay is zero before the record starts (F_{-1} = 0).  With
+ * a pulsed laser whose period T is not long against tau, the remainder exp(-T/tau) of every earlier pulse's decay lies under
+ * the record ("incomplete decays").  VP_BASIS_EXP_DECAY_IRF_PERIODIC = 11 is the steady state of that pulse train: one
+ * parameter tau, uniform grids only, rectangle rule, lag 0 included, no factor dt -- like kind 9.  The response is taken as
+ * zero outside the record and repeats with period T in the units of the grid; P = T/dt bins, real, P >= m; rho = exp(-dt/tau):
+ *     Phi_i      = sum_{p>=0} sum_k irf_k rho^(i-k+pP)   (terms with i-k+pP >= 0)   = F_i^lin + rho^(i+1) F_{-1}
+ *     dPhi_i/dtau = (dt/tau^2) H_i,   H_i = H_i^lin + rho^(i+1) (H_{-1} + (i+1) F_{-1})
+ * i.e. the recurrence of kind 9, F_i = irf_i + rho F_{i-1}, H_i = rho (H_{i-1} + F_{i-1}), started from
+ *     A = F^lin_{m-1}, B = H^lin_{m-1}                  (the totals of the zero-start recurrence at row m-1)
+ *     g = P - m (bins), e = exp(-(T - m dt)/tau)        (exactly 1 when g = 0)
+ *     E = exp(-T/tau),  D = -expm1(-T/tau)
+ *     F_{-1} = e A / D,   H_{-1} = (e/D) (g A + B + P E A / D)
+ * The period belongs to the handle (vp_set_irf_period): 0, the default, means that the record is exactly one period,
+ * T = m dt_b per grid (g = 0, e = 1 exactly); otherwise T = period for the whole batch.  Host-pointer grids are checked:
+ * period < m dt_b (1 - 1e-6) on any grid is VP_ERR_INVALID; within that band g is taken as 0.  Device-pointer grids are the
+ * caller's contract: g < -1e-6 m gives NaN columns, latched per problem like tau <= 0.  A descriptor with this kind needs
+ * m >= 2 (m = 1: dt = 0, the periodic sum diverges) -- creation answers VP_ERR_INVALID -- and may mix kinds 9, 10 and 11.
  *
  * Parameters for which Phi is not finite (a NaN guess; p1 = 0 with p0 on a grid point: 0 / 0) are latched per problem in
  * status[b], like a caller's non-finite columns; p1 = 0 elsewhere gives a finite Phi (exp(-inf) = 0) whose Gaussian
@@ -322,6 +343,12 @@ int vp_set_bounds(vp_batch *h, const double *lower, const double *upper, int per
  * be called again to replace the response (the next frame of a stream, with vp_set_observations); every cached evaluation /
  * fit is invalidated.  VP_ERR_INVALID: null irf, a handle without these kinds, a stepped fit in progress. */
 int vp_set_irf(vp_batch *h, const void *irf, int per_problem);
+
+/* The period T of VP_BASIS_EXP_DECAY_IRF_PERIODIC in the units of the grid, shared by the batch (see "Periodic IRF
+ * reconvolution" above).  0 (the default): the record is exactly one period, T = m dt_b per grid.  Every cached evaluation /
+ * fit is invalidated, as by vp_set_irf.  VP_ERR_INVALID: a handle whose model has no periodic kind, a NaN or negative period,
+ * a stepped fit in progress, and -- host-pointer grids -- period < m dt_b (1 - 1e-6) on any grid. */
+int vp_set_irf_period(vp_batch *h, double period);
 
 /*
  * Start-point search: rank K candidate parameter vectors per problem ON THE DEVICE and leave the best one in the handle.

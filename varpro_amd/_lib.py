@@ -28,7 +28,7 @@ VP_BASIS_SKIP_INVARIANT = 1
 VP_SEARCH_PER_PROBLEM = 1
 VP_BASIS_CONST, VP_BASIS_EXP_DECAY, VP_BASIS_EXP_RATE, VP_BASIS_EXP_COS, VP_BASIS_SIN_PHASE, VP_BASIS_EXTERNAL = 0, 1, 2, 3, 4, 5
 VP_BASIS_GAUSS, VP_BASIS_LORENTZ, VP_BASIS_LINEAR = 6, 7, 8
-VP_BASIS_EXP_DECAY_IRF, VP_BASIS_IRF = 9, 10
+VP_BASIS_EXP_DECAY_IRF, VP_BASIS_IRF, VP_BASIS_EXP_DECAY_IRF_PERIODIC = 9, 10, 11
 VP_FIT_DERIVATIVES_ON_ACCEPT = 1
 VP_WANT_BASIS, VP_WANT_DERIVATIVES = 1, 2
 VP_KERNEL_EVALUATE, VP_KERNEL_BASIS, VP_KERNEL_FIT = 0, 1, 2
@@ -54,7 +54,7 @@ ABI_SYMBOLS = [
     "vp_last_error_detail", "vp_version", "vp_device_count",
     "vp_batch_create_external", "vp_set_params_with_basis", "vp_jacobian_with_derivatives", "vp_evaluate_with_basis",
     "vp_reduce_cost", "vp_fit_begin", "vp_fit_step_with_basis", "vp_fit_end", "vp_fit_active_set", "vp_global_statistics",
-    "vp_set_bounds", "vp_search", "vp_set_irf",
+    "vp_set_bounds", "vp_search", "vp_set_irf", "vp_set_irf_period",
 ]
 
 
@@ -134,6 +134,8 @@ def load():
         lib.vp_set_bounds.argtypes = [vp, dp, dp, C.c_int]
     if hasattr(lib, "vp_set_irf"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no IRF kinds)
         lib.vp_set_irf.argtypes = [vp, vp, C.c_int]
+    if hasattr(lib, "vp_set_irf_period"):  # (... or no periodic IRF kind)
+        lib.vp_set_irf_period.argtypes = [vp, C.c_double]
     if hasattr(lib, "vp_search"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no search)
         lib.vp_search.argtypes = [vp, vp, C.c_int64, C.c_int, vp, vp, vp]
         lib.vp_debug_search_ms.argtypes = [vp, C.POINTER(C.c_float)]

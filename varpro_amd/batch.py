@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, bounds as _bounds
-from .model import basis as _basis, check_irf as _check_irf, uniform_step as _uniform_step
+from .model import basis as _basis, check_irf as _check_irf, check_irf_period as _check_irf_period, uniform_step as _uniform_step
 from ._lib import check
 
 try:
@@ -134,11 +134,13 @@ def _device_entry(fn):
 
 class BatchProblem:
     def __init__(self, model, Y, x=None, weights=None, epsilon=None, device=0, grid_recurrence=True, stream_rows=False,
-                 device_columns=False, irf=None):
+                 device_columns=False, irf=None, irf_period=None):
         """model: varpro_amd.SeparableModel; Y: (B, m) or (B, S, m); x: (m,) shared grid or (B, m)
         per-problem grids (default: model.x); weights: None (unit), (m,) or (B, m).
         irf: the instrument response of a model with ``basis.EXP_DECAY_IRF`` / ``basis.IRF``, (m,) shared or (B, m)
         (``set_irf`` sets or replaces it later); such a model needs a uniform grid.
+        irf_period: the period T >= m dt of ``basis.EXP_DECAY_IRF_PERIODIC`` in the units of the grid (``set_irf_period``);
+        None or 0: the record is exactly one period.
         grid_recurrence=False sets VP_FLAG_NO_GRID_RECURRENCE (per-row exponentials even on uniform grids).
         device_columns=True sets VP_FLAG_DEVICE_COLUMNS: a descriptor of the exponential / trigonometric kinds alone becomes a
         device-column handle too, which takes ``set_bounds``."""
@@ -202,8 +204,12 @@ class BatchProblem:
                 raise ValueError("irf given, but the model has no basis.EXP_DECAY_IRF / basis.IRF function")
             irf = self._as_array(irf)
             _check_irf(irf, self.B, self.m)
+        self._grid_step = None
         if self.irf_kinds and not self.device_mode:
-            _uniform_step(x)  # (a device grid is the caller's contract: include/varpro_hip.h)
+            self._grid_step = _uniform_step(x)  # (a device grid is the caller's contract: include/varpro_hip.h)
+        self.irf_periodic = (not self.external) and _basis.EXP_DECAY_IRF_PERIODIC in model.kinds
+        if irf_period is not None:
+            irf_period = self._checked_irf_period(irf_period)
         self._keep = (x, Y, w)
         stream = None
         if self.device_mode:
@@ -227,6 +233,8 @@ class BatchProblem:
         self._h = h
         self._have_params = False  # mirrors the handle: set_params / evaluate / fit has run on the current data
         self._keep = None  # the handle owns copies (Y_w = W*Y, t, w)
+        if irf_period is not None:
+            self.set_irf_period(irf_period)
         if irf is not None:
             self.set_irf(irf)
 
@@ -641,6 +649,20 @@ class BatchProblem:
             raise ValueError("set_irf: the model has no basis.EXP_DECAY_IRF / basis.IRF function")
         irf, per_problem = _check_irf(self._as_array(irf), self.B, self.m)
         check(self.lib.vp_set_irf(self._h, self._ptr(irf), int(per_problem)))
+        self._have_params = False
+
+    def _checked_irf_period(self, period):
+        if not self.irf_periodic:
+            raise ValueError("irf_period: the model has no basis.EXP_DECAY_IRF_PERIODIC function")
+        return _check_irf_period(period, self.m, self._grid_step)
+
+    @_device_entry
+    def set_irf_period(self, period):
+        """the period T of ``basis.EXP_DECAY_IRF_PERIODIC`` in the units of the grid, shared by the batch
+        (vp_set_irf_period); None or 0: the record is exactly one period, T = m dt per grid.  ValueError: NaN, a negative
+        value, a model without the kind, a host grid with T < m dt.  Cached results are invalidated."""
+        period = self._checked_irf_period(period)
+        check(self.lib.vp_set_irf_period(self._h, C.c_double(period)))
         self._have_params = False
 
     def set_bounds(self, lower, upper):

@@ -43,7 +43,9 @@ enum class Basis : int32_t {
     // IRF reconvolution on a uniform grid (BatchProblem::set_irf): the decay exp(-t/tau) convolved with the instrument
     // response -- sum_{k<=i} irf_k exp(-(i-k) dt/tau), no factor dt -- and the response itself (the scattered-light term)
     ExpDecayIrf = VP_BASIS_EXP_DECAY_IRF,
-    Irf = VP_BASIS_IRF
+    Irf = VP_BASIS_IRF,
+    // ... with the response repeating every period T >= m dt (BatchProblem::set_irf_period; default: the record is one period)
+    ExpDecayIrfPeriodic = VP_BASIS_EXP_DECAY_IRF_PERIODIC
 };
 inline int arity(Basis k) {
     switch (k) {
@@ -52,7 +54,8 @@ inline int arity(Basis k) {
     case Basis::Irf: return 0;
     case Basis::ExpDecay:
     case Basis::ExpRate:
-    case Basis::ExpDecayIrf: return 1;
+    case Basis::ExpDecayIrf:
+    case Basis::ExpDecayIrfPeriodic: return 1;
     default: return 2;
     }
 }
@@ -341,6 +344,8 @@ class BatchProblem {
         if ((int64_t)irf.size() != m && !per_problem) throw std::invalid_argument("irf must hold m or B*m values");
         check(vp_set_irf(h_, irf.data(), per_problem ? 1 : 0));
     }
+    // the period T >= m dt of Basis::ExpDecayIrfPeriodic in the units of the grid (vp_set_irf_period); 0: the record is one period
+    void set_irf_period(double period) { check(vp_set_irf_period(h_, period)); }
     // start-point search (vp_search): per problem the best of K candidates by the projected objective; the handle is then
     // in the state of set_params(result.alpha).  candidates: K*q values shared by all problems, or B*K*q with per_problem
     struct SearchResult {

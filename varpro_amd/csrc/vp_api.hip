@@ -346,6 +346,10 @@ struct __attribute__((visibility("hidden"))) vp_batch {
     bool have_irf = false;   // vp_set_irf has been called
     void *d_irf = nullptr;   // [rows] or [B][rows] of the handle's dtype (sized for the per-problem form at the first call)
     int64_t irf_stride = 0;  // 0: one response for all problems, rows: per problem
+    // VP_BASIS_EXP_DECAY_IRF_PERIODIC: the period of vp_set_irf_period (0: the record is one period) and, for a host grid,
+    // the longest record m dt_b of the batch (< 0: a device grid, the caller's contract)
+    bool irf_periodic = false;
+    double irf_period = 0.0, irf_span_max = -1.0;
     // batched reverse-communication LM fit of a caller-evaluated model (vp_fit_begin / vp_fit_step_with_basis / vp_fit_end)
     void *d_xf_state = nullptr;      // [B] LM records of the step kernel
     void *d_xf_trial = nullptr;      // [B][q] trial points of the last step
@@ -648,12 +652,13 @@ void fill_cols_params(const vp_batch *h, ColsParams &c) {
     c.B = h->B;
     c.irf = h->d_irf;
     c.irf_stride = h->irf_stride;
+    c.irf_period = h->irf_period;
     c.stream = h->stream;
 }
 // a handle with an IRF kind cannot evaluate a column before vp_set_irf
 #define VP_NEEDS_IRF(h, what)                                                                                          \
     if ((h)->irf_kinds && !(h)->have_irf)                                                                              \
-    return fail(VP_ERR_INVALID, what ": the model has an IRF reconvolution kind (VP_BASIS_EXP_DECAY_IRF / VP_BASIS_IRF) "  \
+    return fail(VP_ERR_INVALID, what ": the model has an IRF reconvolution kind (VP_BASIS_EXP_DECAY_IRF[_PERIODIC] / VP_BASIS_IRF) " \
                                      "and the handle has no instrument response yet: call vp_set_irf first")
 // Phi and dPhi of `alpha_dev` [B][q] into the handle's own buffers, which become the columns of the caller-evaluated path.
 // list / count (device): only these problems, `bound` an upper bound of *count; null: all B
@@ -1197,6 +1202,12 @@ static int batch_create(vp_batch **out, const vp_model_desc *model, int dtype, i
                         const void *Y, const void *w, double svd_epsilon, int flags, int device, void *hip_stream,
                         const ExtSpec *ext) {
     const bool dev_data = (flags & VP_FLAG_DEVICE_PTRS) != 0;
+    double irf_span_max = -1.0; // a host grid: the longest record m dt_b (vp_set_irf_period checks the period against it)
+    if (model && !ext && model->n_basis > 0 && model->n_basis <= VP_MAX_BASIS && m == 1)
+        for (int j = 0; j < model->n_basis; ++j)
+            if (model->kind[j] == VP_BASIS_EXP_DECAY_IRF_PERIODIC)
+                return fail(VP_ERR_INVALID, "VP_BASIS_EXP_DECAY_IRF_PERIODIC needs m >= 2: one sample has dt = 0, the periodic sum "
+                                            "diverges");
     // the IRF reconvolution kinds need a uniform grid; a host grid is checked here (a device grid is the caller's contract)
     if (model && !ext && t && !dev_data && m > 0 && B > 0 && (dtype == VP_F64 || dtype == VP_F32) && model->n_basis > 0 &&
         model->n_basis <= VP_MAX_BASIS) {
@@ -1212,12 +1223,16 @@ static int batch_create(vp_batch **out, const vp_model_desc *model, int dtype, i
                 if (!(std::fabs(at(i) - t0 - (double)i * dt) <= 1e-6 * std::fabs(dt)) && m > 1)
                     return fail(VP_ERR_INVALID, "the IRF reconvolution kinds (VP_BASIS_EXP_DECAY_IRF / VP_BASIS_IRF) need a uniform "
                                                 "grid: |t_i - t_0 - i dt| <= 1e-6 |dt| with dt = (t[m-1] - t[0]) / (m-1)");
+            irf_span_max = std::max(irf_span_max, (double)m * dt);
         }
     }
     // (arguments batch_create_impl refuses go to it as they are, for its message)
     if (!out || !model || !Y || (!t && !ext) || m <= 0 || S <= 0 || B <= 0 || (dtype != VP_F64 && dtype != VP_F32) ||
-        m >= model->n_basis || model->n_basis > VP_MAX_BASIS)
-        return batch_create_impl(out, model, dtype, m, S, B, t, Y, w, svd_epsilon, flags, device, hip_stream, dev_data, ext);
+        m >= model->n_basis || model->n_basis > VP_MAX_BASIS) {
+        const int rc = batch_create_impl(out, model, dtype, m, S, B, t, Y, w, svd_epsilon, flags, device, hip_stream, dev_data, ext);
+        if (rc == VP_ERR_OK && out && *out) (*out)->irf_span_max = irf_span_max;
+        return rc;
+    }
     PaddedInputs pad;
     DeviceGuard guard;
     hipStream_t st = nullptr;
@@ -1231,7 +1246,10 @@ static int batch_create(vp_batch **out, const vp_model_desc *model, int dtype, i
         return rc;
     const int rc = batch_create_impl(out, model, dtype, model->n_basis, S, B, t ? pad.t.data() : nullptr, pad.y.data(),
                                      pad.w.data(), svd_epsilon, flags, device, hip_stream, false, ext);
-    if (rc == VP_ERR_OK) (*out)->m_user = m;
+    if (rc == VP_ERR_OK) {
+        (*out)->m_user = m;
+        (*out)->irf_span_max = irf_span_max;
+    }
     return rc;
 }
 
@@ -1480,6 +1498,8 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
         h->col_model = *descriptor;
         for (int j = 0; j < descriptor->n_basis; ++j)
             if (is_irf_kind(descriptor->kind[j])) h->irf_kinds = true;
+        for (int j = 0; j < descriptor->n_basis; ++j)
+            if (descriptor->kind[j] == VP_BASIS_EXP_DECAY_IRF_PERIODIC) h->irf_periodic = true;
     }
     if (int rc = batch_init(h, t, Y, w, hip_stream, data_on_device)) {
         vp_batch_destroy(h);
@@ -2141,6 +2161,22 @@ int vp_set_irf(vp_batch *h, const void *irf, int per_problem) {
     return VP_ERR_OK;
 }
 
+int vp_set_irf_period(vp_batch *h, double period) {
+    VP_ENTER(h);
+    if (!h->irf_periodic)
+        return fail(VP_ERR_INVALID, "vp_set_irf_period: the handle's model has no VP_BASIS_EXP_DECAY_IRF_PERIODIC");
+    if (!(period >= 0.0)) return fail(VP_ERR_INVALID, "vp_set_irf_period: the period must be 0 (the record is one period) or positive");
+    if (h->xf_running) return fail(VP_ERR_INVALID, "vp_set_irf_period during a stepped fit");
+    if (period > 0.0 && h->irf_span_max >= 0.0 && period < h->irf_span_max * (1.0 - 1e-6))
+        return fail(VP_ERR_INVALID, "vp_set_irf_period: the period is shorter than the record, period < m dt (1 - 1e-6)");
+    h->irf_period = period;
+    // the cached evaluation / fit and the handle's columns belong to the old period
+    invalidate(h);
+    h->ext_phi = nullptr;
+    h->ext_dphi = nullptr;
+    return VP_ERR_OK;
+}
+
 // ---- start-point search (vp_search.hpp) ---------------------------------------------------------------------------------
 namespace {
 
@@ -2671,6 +2707,7 @@ static int kind_arity(int kind) {
     case VP_BASIS_LINEAR: return 0;
     case VP_BASIS_EXP_DECAY_IRF: return 1;
     case VP_BASIS_IRF: return 0;
+    case VP_BASIS_EXP_DECAY_IRF_PERIODIC: return 1;
     default: return -1; // (VP_BASIS_EXTERNAL never reaches a descriptor: vp_batch_create_external only)
     }
 }

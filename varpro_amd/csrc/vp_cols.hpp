@@ -4,7 +4,7 @@
 // downstream of the columns is done by the caller-evaluated kernels (vp_ext.hpp, vp_blk_ext.hpp, vp_extfit.hpp, ...) exactly
 // as for a caller's columns.  All eight device kinds are evaluated here, so a descriptor may mix a Gaussian with an
 // exponential tail and a baseline.
-// (The two IRF reconvolution kinds are not pointwise functions of t: their columns come from the scan kernel of vp_irf.hpp,
+// (The IRF reconvolution kinds are not pointwise functions of t: their columns come from the scan kernel of vp_irf.hpp,
 // launched behind this one by cols_fill; launch_fill below keeps them out of the descriptor this kernel sees.)
 //
 // Work sharing: a THREAD owns one 16-byte row group (2 fp64 / 4 fp32 rows) of one problem and walks over ALL basis functions
@@ -50,12 +50,15 @@ struct ColsParams {
     int64_t bound_stride;  // 0: one box for all problems, q: per problem
     const void *irf;       // descriptors with an IRF kind: the response, [m] or [B][irf_stride] (vp_irf.hpp)
     int64_t irf_stride;    // 0: one response for all problems
+    double irf_period;     // VP_BASIS_EXP_DECAY_IRF_PERIODIC: the period in grid units, 0: the record is one period
     hipStream_t stream;
 };
 // every column of the descriptor: cols_fill_kernel for the pointwise kinds, then the scan kernel for the IRF kinds
 int cols_fill(const ColsParams &p);
 int irf_cols_fill(const ColsParams &p); // the columns of the IRF kinds alone (vp_irf.hpp)
-inline bool is_irf_kind(const int kind) { return kind == VP_BASIS_EXP_DECAY_IRF || kind == VP_BASIS_IRF; }
+inline bool is_irf_kind(const int kind) {
+    return kind == VP_BASIS_EXP_DECAY_IRF || kind == VP_BASIS_IRF || kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC;
+}
 // in place on x [B][q] (the handle's dtype): x <- g^-1(x) (to_internal != 0) or x <- g(x), the maps of bound_map / bound_unmap
 int bounds_transform(int dtype, void *x, const void *lo, const void *hi, int64_t bound_stride, int q, int64_t B, int to_internal,
                      hipStream_t stream);
@@ -438,7 +441,7 @@ template <typename T> int launch_fill(const ColsParams &p) {
     };
     // The kernel numbers its derivative columns by counting the parameters of the functions it walks, so the functions of
     // the IRF kinds -- whose columns come from the scan kernel (vp_irf.hpp) -- are taken out of the descriptor it sees: a
-    // VP_BASIS_IRF simply (it has no parameters), and at every VP_BASIS_EXP_DECAY_IRF the descriptor is cut, the run of
+    // VP_BASIS_IRF simply (it has no parameters), and at every VP_BASIS_EXP_DECAY_IRF[_PERIODIC] the descriptor is cut, the run of
     // functions behind it going to a launch of its own whose dPhi starts at that run's first pair.  A descriptor without
     // these kinds is one run: the launch it always was.
     a.mdl = p.model;
@@ -458,7 +461,7 @@ template <typename T> int launch_fill(const ColsParams &p) {
     for (int j = 0; j < p.model.n_basis; ++j) {
         const int kind = p.model.kind[j];
         if (kind == VP_BASIS_IRF) continue;
-        if (kind == VP_BASIS_EXP_DECAY_IRF) {
+        if (kind == VP_BASIS_EXP_DECAY_IRF || kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC) {
             if (int rc = flush()) return rc;
             continue;
         }

@@ -1,5 +1,5 @@
 // the scan kernel of the IRF reconvolution kinds (vp_irf.hpp): fp64 / fp32 x {16-byte groups, element-wise} x {ordinary,
-// non-temporal stores} x {unbounded, box bounds}
+// non-temporal stores} x {unbounded, box bounds} x {zero start, periodic}
 #include "vp_irf.hpp"
 
 namespace vp {

@@ -32,14 +32,18 @@ class basis:
     # (BatchProblem(..., irf=) / set_irf, SeparableProblemBuilder.instrument_response).  Rectangle rule: lag 0 included, no dt
     EXP_DECAY_IRF = 9   # sum_{k<=i} irf_k rho^(i-k)      the decay exp(-t/p0) convolved with the response
     IRF = 10            # irf_i                 (invariant_function: the scattered-light term)
+    # ... with the response repeating every period T >= m dt (BatchProblem(..., irf_period=) / set_irf_period; default: the
+    # record is one period): the steady state of the pulse train, for decays that outlast the laser period
+    EXP_DECAY_IRF_PERIODIC = 11  # sum_{p>=0} sum_k irf_k rho^(i-k+pP), P = T/dt   (terms with i-k+pP >= 0)
     ARITY = {CONST: 0, EXP_DECAY: 1, EXP_RATE: 1, EXP_COS: 2, SIN_PHASE: 2, GAUSS: 2, LORENTZ: 2, LINEAR: 0,
-             EXP_DECAY_IRF: 1, IRF: 0}
+             EXP_DECAY_IRF: 1, IRF: 0, EXP_DECAY_IRF_PERIODIC: 1}
     NAME = {CONST: "const", EXP_DECAY: "exp_decay", EXP_RATE: "exp_rate", EXP_COS: "exp_cos", SIN_PHASE: "sin_phase",
-            GAUSS: "gauss", LORENTZ: "lorentz", LINEAR: "linear", EXP_DECAY_IRF: "exp_decay_irf", IRF: "irf"}
+            GAUSS: "gauss", LORENTZ: "lorentz", LINEAR: "linear", EXP_DECAY_IRF: "exp_decay_irf", IRF: "irf",
+            EXP_DECAY_IRF_PERIODIC: "exp_decay_irf_periodic"}
     # kinds that need the instrument response
-    IRF_KINDS = (EXP_DECAY_IRF, IRF)
+    IRF_KINDS = (EXP_DECAY_IRF, IRF, EXP_DECAY_IRF_PERIODIC)
     # kinds whose columns the device evaluates into memory (a device-column handle, include/varpro_hip.h)
-    DEVICE_COLUMN = (GAUSS, LORENTZ, LINEAR, EXP_DECAY_IRF, IRF)
+    DEVICE_COLUMN = (GAUSS, LORENTZ, LINEAR, EXP_DECAY_IRF, IRF, EXP_DECAY_IRF_PERIODIC)
 
 
 def uniform_step(x, what="grid"):
@@ -66,31 +70,73 @@ def check_irf(irf, B, m):
     raise ValueError("InvalidLengthOfIrf: the instrument response must have shape (%d,) or (%d, %d), got %r" % (m, B, m, shape))
 
 
-def irf_columns(irf, dt, tau):
+def check_irf_period(period, m=None, dt=None):
+    """the period of basis.EXP_DECAY_IRF_PERIODIC as a float (None / 0: the record is one period); ValueError for NaN, a
+    negative value and, given the steps dt of host grids of m samples, period < m dt (1 - 1e-6) on any of them"""
+    period = 0.0 if period is None else float(period)
+    if not period >= 0:
+        raise ValueError("InvalidIrfPeriod: the period must be 0 (the record is one period) or positive, got %r" % (period,))
+    if period > 0 and dt is not None and np.any(period < m * np.asarray(dt, dtype=np.float64) * (1 - 1e-6)):
+        raise ValueError("InvalidIrfPeriod: the period %r is shorter than the record, m dt = %r"
+                         % (period, float(np.max(m * np.asarray(dt, dtype=np.float64)))))
+    return period
+
+
+def irf_columns(irf, dt, tau, period=None):
     """numpy mirror of the scan kernel (vp_irf.hpp), the plain sequential recurrence in the dtype of irf:
-    F_i = irf_i + rho F_{i-1}, H_i = rho (H_{i-1} + F_{i-1}), rho = exp(-dt/tau) -> (F, dt/tau^2 H)"""
+    F_i = irf_i + rho F_{i-1}, H_i = rho (H_{i-1} + F_{i-1}), rho = exp(-dt/tau) -> (F, dt/tau^2 H).
+    period: None -- F_{-1} = H_{-1} = 0 (basis.EXP_DECAY_IRF); else the periodic form (basis.EXP_DECAY_IRF_PERIODIC) with
+    T = period, 0: T = m dt.  A totals pass gives A = F_{m-1}, B = H_{m-1} of the zero start, then the same recurrence runs
+    from the steady-state carry (include/varpro_hip.h): with g = (T - m dt)/dt, P = m + g, e = exp(-(T - m dt)/tau),
+    E = exp(-T/tau), D = -expm1(-T/tau):  F_{-1} = e A / D,  H_{-1} = (e/D) (g A + B + P E A / D).
+    T < m dt (1 - 1e-6) gives NaN columns, inside that band g = 0."""
     irf = np.asarray(irf)
     T = irf.dtype.type
     dt, tau = T(dt), T(tau)
+    m = irf.size
     F, H = np.empty_like(irf), np.empty_like(irf)
     with np.errstate(all="ignore"):
+        span = T(m) * dt
+        gap = T(0)
+        if period is not None and T(period) > 0:
+            gap = T(period) - span
+            if gap < T(-1e-6) * span:
+                tau = T(np.nan)
+            if not gap > 0:
+                gap = T(0)
         rho = np.exp(-(dt / tau)) if tau > 0 else T(np.nan)
         f = h = T(0)
-        for i in range(irf.size):
+        v = irf
+        if irf.dtype == np.float64:  # (Python floats are IEEE doubles: the same roundings, a faster loop)
+            rho, f, h, v = float(rho), 0.0, 0.0, irf.tolist()
+        if period is not None:
+            for i in range(m):  # the totals of the zero start at row m - 1
+                h = rho * (h + f)
+                f = v[i] + rho * f
+            f, h = T(f), T(h)
+            per = span + gap
+            g = gap / dt
+            e = np.exp(-(gap / tau)) if gap > 0 else T(1)
+            E, D = np.exp(-(per / tau)), -np.expm1(-(per / tau))
+            f, h = (e * f) / D, (e / D) * (g * f + h + (T(m) + g) * E * f / D)
+            if irf.dtype == np.float64:
+                f, h = float(f), float(h)
+        for i in range(m):
             h = rho * (h + f)
-            f = irf[i] + rho * f
+            f = v[i] + rho * f
             F[i], H[i] = f, h
         return F, (dt / (tau * tau)) * H
 
 
-def _kind_columns(kind, x, p0, p1, irf=None):
+def _kind_columns(kind, x, p0, p1, irf=None, irf_period=None):
     """numpy mirror of one basis kind: (f, [df/dp0, df/dp1][:arity]) on the grid x (include/varpro_hip.h)"""
     if kind in basis.IRF_KINDS:
         if irf is None:
             raise ModelError("the model has an IRF reconvolution kind and no instrument response (model.irf)")
         if kind == basis.IRF:
             return np.array(irf, dtype=x.dtype), []
-        f, d = irf_columns(np.asarray(irf, dtype=x.dtype), uniform_step(x), p0)
+        period = (irf_period or 0.0) if kind == basis.EXP_DECAY_IRF_PERIODIC else None
+        f, d = irf_columns(np.asarray(irf, dtype=x.dtype), uniform_step(x), p0, period)
         return f, [d]
     if kind == basis.CONST:
         return np.ones_like(x), []
@@ -149,6 +195,7 @@ class SeparableModel:
         self.x = np.ascontiguousarray(x, dtype=self.dtype).reshape(-1)
         self._alpha = np.ascontiguousarray(initial_parameters, dtype=self.dtype).reshape(-1)
         self.irf = None  # IRF kinds: the response of the single-problem surface (SeparableProblemBuilder.instrument_response)
+        self.irf_period = None  # ... and the period of basis.EXP_DECAY_IRF_PERIODIC (None / 0: the record is one period)
         # dependency pairs in model order (basis-major): the layout of vp_basis' dPhi output
         self.pairs = [(j, a, pi) for j, ps in enumerate(self.param_indices) for a, pi in enumerate(ps)]
 
@@ -195,7 +242,7 @@ class SeparableModel:
         with np.errstate(all="ignore"):
             for j, (kind, ps) in enumerate(zip(self.kinds, self.param_indices)):
                 args = [a[pi] for pi in ps] + [None, None]
-                f, ds = _kind_columns(kind, x, args[0], args[1], self.irf)
+                f, ds = _kind_columns(kind, x, args[0], args[1], self.irf, self.irf_period)
                 phi[0, j] = f
                 for d in ds:
                     dphi[0, pair] = d

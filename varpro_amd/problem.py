@@ -10,7 +10,7 @@ src/problem.rs:57-212 (problem state and accessors), src/solvers/levmar/mod.rs:2
 import numpy as np
 
 from .batch import BatchProblem, STATUS_OK
-from .model import basis
+from .model import basis, check_irf_period, uniform_step
 
 
 class SeparableProblemBuilderError(ValueError):
@@ -24,12 +24,13 @@ class SeparableProblemBuilderError(ValueError):
 class SeparableProblem:
     """One separable least-squares problem living on the GPU (B = 1 batch handle)."""
 
-    def __init__(self, model, Y, weights, epsilon, mrhs, irf=None):
+    def __init__(self, model, Y, weights, epsilon, mrhs, irf=None, irf_period=None):
         self._model = model
         self._mrhs = mrhs
         self._weights = weights
         Yb = Y.T[None, :, :] if mrhs else Y[None, :]  # (1, S, m) / (1, m)
-        self._batch = BatchProblem(model, np.ascontiguousarray(Yb), x=model.x, weights=weights, epsilon=epsilon, irf=irf)
+        self._batch = BatchProblem(model, np.ascontiguousarray(Yb), x=model.x, weights=weights, epsilon=epsilon, irf=irf,
+                                   irf_period=irf_period)
         self.m, self.S, self.n, self.q = self._batch.m, self._batch.S, self._batch.n, self._batch.q
         # build(): initial set_params with the model's current parameters (src/problem/builder.rs:321)
         self.set_params(model.params())
@@ -88,6 +89,7 @@ class SeparableProblemBuilder:
         self._weights = None
         self._epsilon = None
         self._irf = None
+        self._irf_period = None
 
     @classmethod
     def new(cls, model):
@@ -105,9 +107,12 @@ class SeparableProblemBuilder:
         self._weights = np.asarray(w, dtype=self._model.dtype).reshape(-1)
         return self
 
-    def instrument_response(self, irf):
-        """the instrument response of a model with ``basis.EXP_DECAY_IRF`` / ``basis.IRF``: one value per sample"""
+    def instrument_response(self, irf, period=None):
+        """the instrument response of a model with ``basis.EXP_DECAY_IRF`` / ``basis.IRF`` /
+        ``basis.EXP_DECAY_IRF_PERIODIC``: one value per sample.  period: the period of the periodic kind in the units of x
+        (None: the record is one period)"""
         self._irf = np.asarray(irf, dtype=self._model.dtype)
+        self._irf_period = period
         return self
 
     def epsilon(self, eps):
@@ -145,4 +150,11 @@ class SeparableProblemBuilder:
                     "InvalidLengthOfIrf", "The instrument response must be a vector of the length of x (%d), got shape %r"
                     % (x_len, tuple(self._irf.shape)))
             self._model.irf = self._irf.copy()  # (the model surface -- eval / eval_partial_deriv -- mirrors it on the host)
-        return SeparableProblem(self._model, Y, self._weights, self._epsilon, self._mrhs, self._irf)
+        if self._irf_period is not None:
+            if basis.EXP_DECAY_IRF_PERIODIC not in self._model.kinds:
+                raise SeparableProblemBuilderError("UnexpectedIrfPeriod", "the model has no basis.EXP_DECAY_IRF_PERIODIC function")
+            try:
+                self._model.irf_period = check_irf_period(self._irf_period, x_len, uniform_step(self._model.x))
+            except ValueError as e:
+                raise SeparableProblemBuilderError("InvalidIrfPeriod", str(e))
+        return SeparableProblem(self._model, Y, self._weights, self._epsilon, self._mrhs, self._irf, self._irf_period)
