@@ -1863,9 +1863,7 @@ int vp_basis(vp_batch *h, const void *alpha, void *Phi_out, void *dPhi_out, int 
     if (!alpha) return fail(VP_ERR_INVALID, "null alpha");
     const size_t ts = tsize(h->dtype);
     if (h->devcols) { // the column kernel straight into the caller's arrays (host-pointer handles: staged)
-        int nc = 0;
-        for (int j = 0; j < h->n; ++j)
-            if (!((flags & VP_BASIS_SKIP_INVARIANT) && h->col_model.kind[j] == VP_BASIS_CONST)) ++nc;
+        const int nc = column_map(h->col_model, flags & VP_BASIS_SKIP_INVARIANT).n_phi_cols;
         const size_t rows = (size_t)col_rows(h);
         InBuf a;
         if (int rc = a.init(h, alpha, (size_t)h->B * h->q * ts)) return rc;

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/varpro_hip.h"
 #include "vp_model.hpp"
@@ -58,6 +59,25 @@ int cols_fill(const ColsParams &p);
 int irf_cols_fill(const ColsParams &p); // the columns of the IRF kinds alone (vp_irf.hpp)
 inline bool is_irf_kind(const int kind) {
     return kind == VP_BASIS_EXP_DECAY_IRF || kind == VP_BASIS_IRF || kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC;
+}
+// the column numbering of a descriptor: phi_col[j] the Phi column of function j (-1: skipped, a VP_BASIS_CONST under
+// skip_invariant), first_pair[j] its first derivative column in dPhi (pairs in model order), and the totals
+struct ColumnMap {
+    int phi_col[VP_MAX_BASIS], first_pair[VP_MAX_BASIS];
+    int n_phi_cols, n_pairs;
+};
+inline ColumnMap column_map(const vp_model_desc &model, const int skip_invariant) {
+    ColumnMap c;
+    c.n_phi_cols = c.n_pairs = 0;
+    for (int j = 0; j < VP_MAX_BASIS; ++j) {
+        c.phi_col[j] = -1;
+        c.first_pair[j] = c.n_pairs;
+        if (j >= model.n_basis) continue;
+        if (!(skip_invariant && model.kind[j] == VP_BASIS_CONST)) c.phi_col[j] = c.n_phi_cols++;
+        for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k)
+            if (model.param[j][k] >= 0) ++c.n_pairs;
+    }
+    return c;
 }
 // in place on x [B][q] (the handle's dtype): x <- g^-1(x) (to_internal != 0) or x <- g(x), the maps of bound_map / bound_unmap
 int bounds_transform(int dtype, void *x, const void *lo, const void *hi, int64_t bound_stride, int q, int64_t B, int to_internal,
@@ -221,7 +241,13 @@ __device__ __forceinline__ void basis_at(const int kind, const T t, const T p0, 
     }
 }
 
-template <typename T, bool VEC, bool NT> __global__ void __launch_bounds__(256) cols_fill_kernel(const ColsArgs<T> a) {
+// The body of both entry points below.  BND: a.alpha holds the INTERNAL parameters u of a bounded fit -- alpha_k = g(u_k) in
+// front of each basis function (per problem, not per row: uniform over the workgroup) and the chain rule on its derivative
+// columns; everything else is the same statements for both, so a new kind or option of this route is written once.  Sharing
+// the body does change the unbounded kernels' instruction text (operands move) but not what they cost: registers, spills and
+// scratch are equal, the instruction count within one, the columns bit-equal and the device time of the fill and of a fit
+// inside the spread of the separate kernels' own rounds (profiles/cols_shared_body_*.json).
+template <typename T, bool VEC, bool NT, bool BND, typename Args> __device__ __forceinline__ void cols_fill_body(const Args &a) {
     constexpr int VW = Vec<T>::VW;
     const unsigned bpp = (unsigned)a.blocks_per_problem;
     const unsigned slot_local = blockIdx.x / bpp;
@@ -245,71 +271,9 @@ template <typename T, bool VEC, bool NT> __global__ void __launch_bounds__(256) 
         for (int e = 0; e < VW; ++e) tt[e] = tg[i + e < m ? e : 0];
     }
     const int n = a.mdl.n_basis, q = a.mdl.n_params;
-    const T *al = a.alpha + b * q;
-    T *phi = a.phi ? a.phi + b * (int64_t)a.n_phi_cols * m : nullptr;
-    T *dphi = a.dphi ? a.dphi + b * (int64_t)a.n_pairs * m : nullptr;
-    int pair = 0;
-    for (int j = 0; j < n; ++j) {
-        const int kind = a.mdl.kind[j];
-        const int i0 = a.mdl.param[j][0], i1 = a.mdl.param[j][1];
-        const T p0 = i0 >= 0 ? al[i0] : T(0), p1 = i1 >= 0 ? al[i1] : T(0);
-        // what the rows of this group share: the reciprocals of the derivative scalings
-        T c0 = T(0), c1 = T(0);
-        if (kind == VP_BASIS_EXP_DECAY) {
-            c0 = T(1) / (p0 * p0);
-        } else if (kind == VP_BASIS_GAUSS) {
-            const T s2 = p1 * p1;
-            c0 = T(1) / s2;
-            c1 = T(1) / (s2 * p1);
-        } else if (kind == VP_BASIS_LORENTZ) {
-            c0 = p1 * p1;
-        }
-        T f[VW], d0[VW], d1[VW];
-#pragma unroll
-        for (int e = 0; e < VW; ++e) basis_at<T>(kind, tt[e], p0, p1, c0, c1, f[e], d0[e], d1[e]);
-        if (phi && a.phi_col[j] >= 0) store_group<T, VEC, NT>(phi + (int64_t)a.phi_col[j] * m, i, m, f);
-        if (i0 >= 0) {
-            if (dphi) store_group<T, VEC, NT>(dphi + (int64_t)pair * m, i, m, d0);
-            ++pair;
-        }
-        if (i1 >= 0) {
-            if (dphi) store_group<T, VEC, NT>(dphi + (int64_t)pair * m, i, m, d1);
-            ++pair;
-        }
-    }
-}
-
-// The bounded sibling: a.alpha holds the INTERNAL parameters u of a bounded fit.  The statements of cols_fill_kernel with
-// alpha_k = g(u_k) in front of each basis function (per problem, not per row: uniform over the workgroup) and the chain rule
-// on its derivative columns.  A kernel of its own, not a template switch of cols_fill_kernel: sharing the body moved
-// operands in the unbounded kernels' instruction text, which stays what it was (profiles/bounds_isa.json).
-template <typename T, bool VEC, bool NT>
-__global__ void __launch_bounds__(256) cols_fill_bounded_kernel(const ColsBoundArgs<T> a) {
-    constexpr int VW = Vec<T>::VW;
-    const unsigned bpp = (unsigned)a.blocks_per_problem;
-    const unsigned slot_local = blockIdx.x / bpp;
-    const int piece = (int)(blockIdx.x - slot_local * bpp);
-    const int i = VW * (piece * 256 + (int)threadIdx.x);
-    const int m = a.m;
-    if (i >= m) return;
-    int64_t b = a.first + (int64_t)slot_local;
-    if (a.list) {
-        if (b >= (int64_t)*a.count) return;
-        b = a.list[b];
-    }
-    const T *tg = a.t + b * a.t_stride + i;
-    T tt[VW];
-    if constexpr (VEC) {
-        const typename Vec<T>::type tv = *reinterpret_cast<const typename Vec<T>::type *>(tg);
-#pragma unroll
-        for (int e = 0; e < VW; ++e) tt[e] = tv[e];
-    } else {
-#pragma unroll
-        for (int e = 0; e < VW; ++e) tt[e] = tg[i + e < m ? e : 0];
-    }
-    const int n = a.mdl.n_basis, q = a.mdl.n_params;
-    const T *al = a.alpha + b * q; // (internal parameters)
-    const T *lo = a.lo + b * a.bound_stride, *hi = a.hi + b * a.bound_stride;
+    const T *al = a.alpha + b * q; // (BND: internal parameters)
+    const T *lo = nullptr, *hi = nullptr;
+    if constexpr (BND) lo = a.lo + b * a.bound_stride, hi = a.hi + b * a.bound_stride;
     T *phi = a.phi ? a.phi + b * (int64_t)a.n_phi_cols * m : nullptr;
     T *dphi = a.dphi ? a.dphi + b * (int64_t)a.n_pairs * m : nullptr;
     int pair = 0;
@@ -317,8 +281,12 @@ __global__ void __launch_bounds__(256) cols_fill_bounded_kernel(const ColsBoundA
         const int kind = a.mdl.kind[j];
         const int i0 = a.mdl.param[j][0], i1 = a.mdl.param[j][1];
         T p0 = T(0), p1 = T(0), s0 = T(1), s1 = T(1); // s: dalpha/du
-        if (i0 >= 0) bound_map<T>(al[i0], lo[i0], hi[i0], p0, s0);
-        if (i1 >= 0) bound_map<T>(al[i1], lo[i1], hi[i1], p1, s1);
+        if constexpr (BND) {
+            if (i0 >= 0) bound_map<T>(al[i0], lo[i0], hi[i0], p0, s0);
+            if (i1 >= 0) bound_map<T>(al[i1], lo[i1], hi[i1], p1, s1);
+        } else {
+            p0 = i0 >= 0 ? al[i0] : T(0), p1 = i1 >= 0 ? al[i1] : T(0);
+        }
         // what the rows of this group share: the reciprocals of the derivative scalings
         T c0 = T(0), c1 = T(0);
         if (kind == VP_BASIS_EXP_DECAY) {
@@ -334,8 +302,10 @@ __global__ void __launch_bounds__(256) cols_fill_bounded_kernel(const ColsBoundA
 #pragma unroll
         for (int e = 0; e < VW; ++e) {
             basis_at<T>(kind, tt[e], p0, p1, c0, c1, f[e], d0[e], d1[e]);
-            d0[e] *= s0;
-            d1[e] *= s1;
+            if constexpr (BND) {
+                d0[e] *= s0;
+                d1[e] *= s1;
+            }
         }
         if (phi && a.phi_col[j] >= 0) store_group<T, VEC, NT>(phi + (int64_t)a.phi_col[j] * m, i, m, f);
         if (i0 >= 0) {
@@ -347,6 +317,13 @@ __global__ void __launch_bounds__(256) cols_fill_bounded_kernel(const ColsBoundA
             ++pair;
         }
     }
+}
+template <typename T, bool VEC, bool NT> __global__ void __launch_bounds__(256) cols_fill_kernel(const ColsArgs<T> a) {
+    cols_fill_body<T, VEC, NT, false>(a);
+}
+template <typename T, bool VEC, bool NT>
+__global__ void __launch_bounds__(256) cols_fill_bounded_kernel(const ColsBoundArgs<T> a) {
+    cols_fill_body<T, VEC, NT, true>(a);
 }
 
 // x <- g^-1(x) (INV) or x <- g(x), one thread per parameter of one problem
@@ -376,68 +353,63 @@ int launch_bounds_transform(void *x, const void *lo, const void *hi, int64_t bou
     return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
 }
 
+// ---- what the launches of this header and of vp_irf.hpp share ----------------------------------------------------------
+// fn(std::bool_constant...) with the compile-time form of the run-time switches, in their order
+template <typename F> void select_variant(F &&fn) { fn(); }
+template <typename F, typename... Rest> void select_variant(F &&fn, const bool first, const Rest... rest) {
+    if (first) select_variant([&](auto... c) { fn(std::true_type{}, c...); }, rest...);
+    else select_variant([&](auto... c) { fn(std::false_type{}, c...); }, rest...);
+}
+// 16-byte groups need m to be a multiple of the group and every array (`src`: the array the kernel reads row-wise; each
+// column starts a multiple of m from its base) 16-byte aligned
+template <typename T> bool vec_groups(const ColsParams &p, const void *src, const int64_t src_stride) {
+    auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    return p.m % Vec<T>::VW == 0 && al16(src) && al16(p.phi) && al16(p.dphi) && (src_stride % Vec<T>::VW) == 0;
+}
+// launch(first, nb) over the B problems in pieces of at most per_launch: what one grid of at most 2^31 - 1 workgroups covers
+template <typename F> int launch_chunks(const int64_t B, const int64_t per_launch, F &&launch) {
+    for (int64_t first = 0; first < B; first += per_launch) {
+        launch(first, B - first < per_launch ? B - first : per_launch);
+        if (hipGetLastError() != hipSuccess) return VP_ERR_HIP;
+    }
+    return VP_ERR_OK;
+}
+
 template <typename T> int launch_fill(const ColsParams &p) {
     constexpr int VW = Vec<T>::VW;
     if (p.B <= 0 || p.m <= 0 || (!p.phi && !p.dphi)) return VP_ERR_OK;
-    ColsArgs<T> a;
-    const bool bounded = p.lo && p.hi;
-    int phi_col[VP_MAX_BASIS], first_pair[VP_MAX_BASIS];
-    int ncols = 0, npairs = 0;
-    for (int j = 0; j < VP_MAX_BASIS; ++j) {
-        phi_col[j] = -1;
-        first_pair[j] = npairs;
-        if (j >= p.model.n_basis) continue;
-        if (!(p.skip_invariant && p.model.kind[j] == VP_BASIS_CONST)) phi_col[j] = ncols++;
-        for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k)
-            if (p.model.param[j][k] >= 0) ++npairs;
-    }
-    a.n_phi_cols = ncols;
+    ColsBoundArgs<T> a; // (the unbounded kernel takes its ColsArgs part)
+    const ColumnMap map = column_map(p.model, p.skip_invariant);
+    const int npairs = map.n_pairs;
+    a.n_phi_cols = map.n_phi_cols;
     a.n_pairs = npairs;
     a.t = (const T *)p.t;
     a.alpha = (const T *)p.alpha;
-    a.phi = ncols > 0 ? (T *)p.phi : nullptr;
+    a.phi = map.n_phi_cols > 0 ? (T *)p.phi : nullptr;
     a.list = p.list;
     a.count = p.count;
     a.t_stride = p.t_stride;
     a.m = p.m;
     a.blocks_per_problem = (p.m + 256 * VW - 1) / (256 * VW);
+    a.lo = (const T *)p.lo;
+    a.hi = (const T *)p.hi;
+    a.bound_stride = p.bound_stride;
     if (!a.phi && !(npairs > 0 && p.dphi)) return VP_ERR_OK;
-    // 16-byte groups need m to be a multiple of the group and every array (each column starts a multiple of m from its base)
-    // 16-byte aligned
-    auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool vec = p.m % VW == 0 && al16(p.t) && al16(p.phi) && al16(p.dphi) && (p.t_stride % VW) == 0;
-    const int64_t per_launch = ((int64_t)0x7fffffff / a.blocks_per_problem); // problems one grid can cover
+    const bool vec = vec_groups<T>(p, p.t, p.t_stride), bounded = p.lo && p.hi;
     // one launch over the functions a.mdl lists, its derivative columns from pair `pair0` of the problem on
     auto launch = [&](const int pair0) -> int {
         a.dphi = npairs > 0 && p.dphi ? (T *)p.dphi + (int64_t)pair0 * p.m : nullptr;
         if (!a.phi && !a.dphi) return VP_ERR_OK;
-        for (int64_t first = 0; first < p.B; first += per_launch) {
-            const int64_t nb = p.B - first < per_launch ? p.B - first : per_launch;
+        return launch_chunks(p.B, (int64_t)0x7fffffff / a.blocks_per_problem, [&](const int64_t first, const int64_t nb) {
             a.first = first;
             const dim3 grid((unsigned)(nb * a.blocks_per_problem)), block(256);
-            if (bounded) {
-                ColsBoundArgs<T> ba;
-                static_cast<ColsArgs<T> &>(ba) = a;
-                ba.lo = (const T *)p.lo;
-                ba.hi = (const T *)p.hi;
-                ba.bound_stride = p.bound_stride;
-                if (vec) {
-                    if (p.nt) hipLaunchKernelGGL((cols_fill_bounded_kernel<T, true, true>), grid, block, 0, p.stream, ba);
-                    else hipLaunchKernelGGL((cols_fill_bounded_kernel<T, true, false>), grid, block, 0, p.stream, ba);
-                } else {
-                    if (p.nt) hipLaunchKernelGGL((cols_fill_bounded_kernel<T, false, true>), grid, block, 0, p.stream, ba);
-                    else hipLaunchKernelGGL((cols_fill_bounded_kernel<T, false, false>), grid, block, 0, p.stream, ba);
-                }
-            } else if (vec) {
-                if (p.nt) hipLaunchKernelGGL((cols_fill_kernel<T, true, true>), grid, block, 0, p.stream, a);
-                else hipLaunchKernelGGL((cols_fill_kernel<T, true, false>), grid, block, 0, p.stream, a);
-            } else {
-                if (p.nt) hipLaunchKernelGGL((cols_fill_kernel<T, false, true>), grid, block, 0, p.stream, a);
-                else hipLaunchKernelGGL((cols_fill_kernel<T, false, false>), grid, block, 0, p.stream, a);
-            }
-            if (hipGetLastError() != hipSuccess) return VP_ERR_HIP;
-        }
-        return VP_ERR_OK;
+            select_variant(
+                [&](auto V, auto N, auto BD) {
+                    if constexpr (BD.value) hipLaunchKernelGGL((cols_fill_bounded_kernel<T, V.value, N.value>), grid, block, 0, p.stream, a);
+                    else hipLaunchKernelGGL((cols_fill_kernel<T, V.value, N.value>), grid, block, 0, p.stream, static_cast<const ColsArgs<T> &>(a));
+                },
+                vec, p.nt != 0, bounded);
+        });
     };
     // The kernel numbers its derivative columns by counting the parameters of the functions it walks, so the functions of
     // the IRF kinds -- whose columns come from the scan kernel (vp_irf.hpp) -- are taken out of the descriptor it sees: a
@@ -465,11 +437,11 @@ template <typename T> int launch_fill(const ColsParams &p) {
             if (int rc = flush()) return rc;
             continue;
         }
-        if (run == 0) run_pair0 = first_pair[j];
+        if (run == 0) run_pair0 = map.first_pair[j];
         a.mdl.kind[run] = kind;
         for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k) a.mdl.param[run][k] = p.model.param[j][k];
-        a.phi_col[run] = phi_col[j];
-        if ((a.phi && phi_col[j] >= 0) || (p.dphi && (p.model.param[j][0] >= 0 || p.model.param[j][1] >= 0))) stores = true;
+        a.phi_col[run] = map.phi_col[j];
+        if ((a.phi && map.phi_col[j] >= 0) || (p.dphi && (p.model.param[j][0] >= 0 || p.model.param[j][1] >= 0))) stores = true;
         ++run;
     }
     if (int rc = flush()) return rc;

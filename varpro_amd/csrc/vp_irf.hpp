@@ -81,7 +81,15 @@ __device__ __forceinline__ void load_group(const T *__restrict__ src, const int 
     }
 }
 
-template <typename T, bool VEC, bool NT, bool BND> __global__ void __launch_bounds__(256) irf_cols_kernel(const IrfArgs<T> a) {
+// The body of both entry points below.  PER: every function of the launch is a VP_BASIS_EXP_DECAY_IRF_PERIODIC (launch_irf),
+// `period` in grid units or 0.  The tile loop is written once (`scan`): the zero-start kernel runs it once, the periodic
+// kernel twice -- without stores for the totals at row m-1, then from the steady-state carry.  The entry points keep their
+// names and argument records; the body is shared although that changes the zero-start kernels' instruction text, because
+// it costs them nothing: no kernel of the family needs more registers, spills or scratch than with a body of its own (14 need
+// 1 to 6 VGPRs fewer), the columns are bit-equal and the device time of the fill and of a fit lies inside the spread of the
+// separate kernels' own rounds (profiles/cols_shared_body_*.json).
+template <typename T, bool VEC, bool NT, bool BND, bool PER>
+__device__ __forceinline__ void irf_cols_body(const IrfArgs<T> &a, const T period) {
     constexpr int VW = Vec<T>::VW, TILE = 64 * VW;
     const int lane = (int)(threadIdx.x & 63u);
     const unsigned wave = blockIdx.x * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -97,117 +105,18 @@ template <typename T, bool VEC, bool NT, bool BND> __global__ void __launch_boun
     const int m = a.m;
     const T *irf = a.irf + b * a.irf_stride;
     T *phi = (a.phi && a.phi_col[f] >= 0) ? a.phi + (b * (int64_t)a.n_phi_cols + a.phi_col[f]) * m : nullptr;
-    if (a.kind[f] == VP_BASIS_IRF) { // the response itself: a copy
-        if (!phi) return;
-        for (int base = 0; base < m; base += TILE) {
-            const int i = base + VW * lane;
-            T x[VW];
-            load_group<T, VEC>(irf, i, m, x);
-            if (i < m) store_group<T, VEC, NT>(phi, i, m, x);
-        }
-        return;
-    }
-    T *dphi = a.dphi ? a.dphi + (b * (int64_t)a.n_pairs + a.pair[f]) * m : nullptr;
-    // ---- what the function's rows share (wave-uniform) ----
-    const int pi = a.param[f];
-    T tau = a.alpha[b * a.q + pi], dtau_du = T(1);
-    if constexpr (BND) bound_map<T>(tau, a.lo[b * a.bound_stride + pi], a.hi[b * a.bound_stride + pi], tau, dtau_du);
-    if (!(tau > T(0))) tau = T(0) / T(0); // tau <= 0, NaN: not a decay -- NaN columns
-    const T *tg = a.t + b * a.t_stride;
-    const T dt = m > 1 ? (tg[m - 1] - tg[0]) / T(m - 1) : T(0);
-    const T rho = cexp(-(dt / tau)); // (tau -> 0+: exp(-inf) = 0, the column is the response)
-    const T dscale = (dt / (tau * tau)) * dtau_du;
-    // rho^(VW d), d = 1, 2, 4, 8, 16 lanes
-    T pw[5];
-    pw[0] = rho * rho;
-    if constexpr (VW == 4) pw[0] *= pw[0];
-#pragma unroll
-    for (int s = 1; s < 5; ++s) pw[s] = pw[s - 1] * pw[s - 1];
-    // the lane's own factor: k groups behind the first lane of its 16-lane row
-    const int k = lane & 15, row = lane >> 4;
-    const T kspan = T(VW * k);
-    const T lf = k == 0 ? T(1) : cexp(-((kspan * dt) / tau));
-    T cF = T(0), cH = T(0); // state at the end of the previous tile (uniform)
-    T xn[VW];
-    load_group<T, VEC>(irf, VW * lane, m, xn);
-    for (int base = 0; base < m; base += TILE) {
-        const int i = base + VW * lane;
-        T x[VW];
-#pragma unroll
-        for (int e = 0; e < VW; ++e) x[e] = xn[e];
-        if (base + TILE < m) load_group<T, VEC>(irf, i + TILE, m, xn); // (the next tile's group, in flight during the scan)
-        // 1. the lane's rows from a zero start
-        T F = T(0), H = T(0);
-#pragma unroll
-        for (int e = 0; e < VW; ++e) {
-            H = rho * (H + F);
-            F = tfma(rho, F, x[e]);
-        }
-        // 2. inclusive scan inside the 16-lane rows, then the rows behind the carry
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            T Fl, Hl;
-            if (s == 0) Fl = dpp<DPP_ROW_SHR + 1>(F), Hl = dpp<DPP_ROW_SHR + 1>(H);
-            else if (s == 1) Fl = dpp<DPP_ROW_SHR + 2>(F), Hl = dpp<DPP_ROW_SHR + 2>(H);
-            else if (s == 2) Fl = dpp<DPP_ROW_SHR + 4>(F), Hl = dpp<DPP_ROW_SHR + 4>(H);
-            else Fl = dpp<DPP_ROW_SHR + 8>(F), Hl = dpp<DPP_ROW_SHR + 8>(H);
-            H = tfma(pw[s], tfma(T(VW << s), Fl, Hl), H);
-            F = tfma(pw[s], Fl, F);
-        }
-        T pF = cF, pH = cH; // prefix of this lane's row
-        {
-            T qF = cF, qH = cH;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const T rF = readlane(F, 16 * r + 15), rH = readlane(H, 16 * r + 15);
-                qH = tfma(pw[4], tfma(T(16 * VW), qF, qH), rH);
-                qF = tfma(pw[4], qF, rF);
-                if (row > r) pF = qF, pH = qH;
+    if constexpr (!PER) {
+        if (a.kind[f] == VP_BASIS_IRF) { // the response itself: a copy
+            if (!phi) return;
+            for (int base = 0; base < m; base += TILE) {
+                const int i = base + VW * lane;
+                T x[VW];
+                load_group<T, VEC>(irf, i, m, x);
+                if (i < m) store_group<T, VEC, NT>(phi, i, m, x);
             }
+            return;
         }
-        // 3. the lane's incoming state, its rows, the carry
-        F = tfma(lf, pF, dpp<DPP_ROW_SHR + 1>(F));
-        H = tfma(lf, tfma(kspan, pF, pH), dpp<DPP_ROW_SHR + 1>(H));
-        T fo[VW], ho[VW];
-#pragma unroll
-        for (int e = 0; e < VW; ++e) {
-            H = rho * (H + F);
-            F = tfma(rho, F, x[e]);
-            fo[e] = F;
-            ho[e] = dscale * H;
-        }
-        if (i < m) {
-            if (phi) store_group<T, VEC, NT>(phi, i, m, fo);
-            if (dphi) store_group<T, VEC, NT>(dphi, i, m, ho);
-        }
-        cF = readlane(F, 63);
-        cH = readlane(H, 63);
     }
-}
-
-// The periodic sibling: every function of its launch is a VP_BASIS_EXP_DECAY_IRF_PERIODIC (launch_irf), `period` in grid
-// units or 0.  The statements of irf_cols_kernel, its tile loop written once (`scan`) and run twice: without stores for the
-// totals at row m-1, then from the steady-state carry.  A kernel of its own, not a compile-time switch of irf_cols_kernel:
-// a template parameter would rename the symbols, and a shared body -- a force-inlined function, a lambda or a textual
-// include -- moved operands in the zero-start kernels' instruction text, which stays what it was
-// (profiles/irf_periodic_isa.json; the same finding as for cols_fill_bounded_kernel).
-template <typename T, bool VEC, bool NT, bool BND>
-__global__ void __launch_bounds__(256) irf_cols_periodic_kernel(const IrfArgs<T> a, const T period) {
-    constexpr int VW = Vec<T>::VW, TILE = 64 * VW;
-    const int lane = (int)(threadIdx.x & 63u);
-    const unsigned wave = blockIdx.x * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const unsigned nf = (unsigned)a.nf;
-    const unsigned slot_local = wave / nf;
-    const int f = (int)(wave - slot_local * nf);
-    if ((int64_t)slot_local >= a.slots) return;
-    int64_t b = a.first + (int64_t)slot_local;
-    if (a.list) {
-        if (b >= (int64_t)*a.count) return;
-        b = a.list[b];
-    }
-    const int m = a.m;
-    const T *irf = a.irf + b * a.irf_stride;
-    T *phi = (a.phi && a.phi_col[f] >= 0) ? a.phi + (b * (int64_t)a.n_phi_cols + a.phi_col[f]) * m : nullptr;
     T *dphi = a.dphi ? a.dphi + (b * (int64_t)a.n_pairs + a.pair[f]) * m : nullptr;
     // ---- what the function's rows share (wave-uniform) ----
     const int pi = a.param[f];
@@ -216,9 +125,9 @@ __global__ void __launch_bounds__(256) irf_cols_periodic_kernel(const IrfArgs<T>
     if (!(tau > T(0))) tau = T(0) / T(0); // tau <= 0, NaN: not a decay -- NaN columns
     const T *tg = a.t + b * a.t_stride;
     const T dt = m > 1 ? (tg[m - 1] - tg[0]) / T(m - 1) : T(0);
-    const T span = T(m) * dt; // the record, and what the period adds to it
+    const T span = T(m) * dt; // (PER) the record, and what the period adds to it
     T gap = T(0);
-    if (period > T(0)) {
+    if (PER && period > T(0)) {
         gap = period - span;
         if (gap < T(-1e-6) * span) tau = T(0) / T(0); // a period shorter than the record: NaN columns
         if (!(gap > T(0))) gap = T(0);                // (inside the tolerance of the uniformity check: one period)
@@ -236,8 +145,8 @@ __global__ void __launch_bounds__(256) irf_cols_periodic_kernel(const IrfArgs<T>
     const T kspan = T(VW * k);
     const T lf = k == 0 ? T(1) : cexp(-((kspan * dt) / tau));
     T cF = T(0), cH = T(0); // state at the end of the previous tile (uniform)
-    T mF = T(0), mH = T(0); // the totals pass: the state at row m-1, in the lane that owns the row
-    // one pass over the response: the totals (no stores), then the columns
+    T mF = T(0), mH = T(0); // (PER) the totals pass: the state at row m-1, in the lane that owns the row
+    // one pass over the response from the carry (cF, cH): the columns, or (PER) the totals without stores
     auto scan = [&](auto stores) {
         constexpr bool STORE = decltype(stores)::value;
         T xn[VW];
@@ -298,8 +207,9 @@ __global__ void __launch_bounds__(256) irf_cols_periodic_kernel(const IrfArgs<T>
             cH = readlane(H, 63);
         }
     };
-    scan(std::false_type{});
-    { // the steady-state carry from the totals at row m-1 (everything wave-uniform)
+    if constexpr (PER) {
+        scan(std::false_type{});
+        // the steady-state carry from the totals at row m-1 (everything wave-uniform)
         const int owner = ((m - 1) % TILE) / VW;
         const T A = readlane(mF, owner), B = readlane(mH, owner);
         const T per = span + gap, g = gap / dt, arg = -(per / tau);
@@ -310,83 +220,68 @@ __global__ void __launch_bounds__(256) irf_cols_periodic_kernel(const IrfArgs<T>
     }
     scan(std::true_type{});
 }
+template <typename T, bool VEC, bool NT, bool BND> __global__ void __launch_bounds__(256) irf_cols_kernel(const IrfArgs<T> a) {
+    irf_cols_body<T, VEC, NT, BND, false>(a, T(0));
+}
+template <typename T, bool VEC, bool NT, bool BND>
+__global__ void __launch_bounds__(256) irf_cols_periodic_kernel(const IrfArgs<T> a, const T period) {
+    irf_cols_body<T, VEC, NT, BND, true>(a, period);
+}
 
 // the columns of the IRF kinds: one launch of irf_cols_kernel over the functions of kinds 9 and 10, one of
 // irf_cols_periodic_kernel over those of kind 11 (a descriptor may mix them; the pairs are numbered over the whole descriptor)
 template <typename T> int launch_irf(const ColsParams &p) {
-    constexpr int VW = Vec<T>::VW;
     if (p.B <= 0 || p.m <= 0 || (!p.phi && !p.dphi)) return VP_ERR_OK;
     if (!p.irf) return VP_ERR_INVALID;
-    const bool bounded = p.lo && p.hi;
-    auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool vec = p.m % VW == 0 && al16(p.irf) && al16(p.phi) && al16(p.dphi) && (p.irf_stride % VW) == 0;
+    const bool vec = vec_groups<T>(p, p.irf, p.irf_stride), bounded = p.lo && p.hi;
+    const ColumnMap map = column_map(p.model, p.skip_invariant);
+    IrfArgs<T> a;
+    a.t = (const T *)p.t;
+    a.alpha = (const T *)p.alpha;
+    a.irf = (const T *)p.irf;
+    a.phi = (T *)p.phi;
+    a.dphi = map.n_pairs > 0 ? (T *)p.dphi : nullptr;
+    a.lo = (const T *)p.lo;
+    a.hi = (const T *)p.hi;
+    a.list = p.list;
+    a.count = p.count;
+    a.t_stride = p.t_stride;
+    a.irf_stride = p.irf_stride;
+    a.bound_stride = p.bound_stride;
+    a.m = p.m;
+    a.q = p.model.n_params;
+    a.n_phi_cols = map.n_phi_cols;
+    a.n_pairs = map.n_pairs;
+    const T period = (T)p.irf_period;
     for (int periodic = 0; periodic < 2; ++periodic) {
-        IrfArgs<T> a;
-        int ncols = 0, npairs = 0, nf = 0;
+        int nf = 0;
         for (int j = 0; j < p.model.n_basis && j < VP_MAX_BASIS; ++j) {
             const int kind = p.model.kind[j];
-            const int col = (p.skip_invariant && kind == VP_BASIS_CONST) ? -1 : ncols++;
             const bool wanted = periodic ? kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC
                                          : (kind == VP_BASIS_IRF ? p.phi != nullptr : kind == VP_BASIS_EXP_DECAY_IRF);
-            if (wanted) {
-                a.kind[nf] = kind;
-                a.phi_col[nf] = col;
-                a.pair[nf] = npairs;
-                a.param[nf] = p.model.param[j][0];
-                ++nf;
-            }
-            for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k)
-                if (p.model.param[j][k] >= 0) ++npairs;
+            if (!wanted) continue;
+            a.kind[nf] = kind;
+            a.phi_col[nf] = map.phi_col[j];
+            a.pair[nf] = map.first_pair[j];
+            a.param[nf] = p.model.param[j][0];
+            ++nf;
         }
         if (nf == 0) continue;
         for (int f = nf; f < VP_MAX_BASIS; ++f) a.kind[f] = a.phi_col[f] = a.pair[f] = a.param[f] = 0;
-        a.t = (const T *)p.t;
-        a.alpha = (const T *)p.alpha;
-        a.irf = (const T *)p.irf;
-        a.phi = (T *)p.phi;
-        a.dphi = npairs > 0 ? (T *)p.dphi : nullptr;
-        a.lo = (const T *)p.lo;
-        a.hi = (const T *)p.hi;
-        a.list = p.list;
-        a.count = p.count;
-        a.t_stride = p.t_stride;
-        a.irf_stride = p.irf_stride;
-        a.bound_stride = p.bound_stride;
-        a.m = p.m;
-        a.q = p.model.n_params;
-        a.n_phi_cols = ncols;
-        a.n_pairs = npairs;
         a.nf = nf;
-        const T period = (T)p.irf_period;
-        const int64_t per_launch = (int64_t)0x7fffffff / nf; // problems one grid can cover (4 waves per workgroup)
-        for (int64_t first = 0; first < p.B; first += per_launch) {
-            const int64_t nb = p.B - first < per_launch ? p.B - first : per_launch;
+        // (4 waves per workgroup)
+        const int rc = launch_chunks(p.B, (int64_t)0x7fffffff / nf, [&](const int64_t first, const int64_t nb) {
             a.first = first;
             a.slots = nb;
             const dim3 grid((unsigned)((nb * nf + 3) / 4)), block(256);
-#define VP_IRF_LAUNCH(V, N, BD)                                                                                        \
-    do {                                                                                                               \
-        if (periodic) hipLaunchKernelGGL((irf_cols_periodic_kernel<T, V, N, BD>), grid, block, 0, p.stream, a, period); \
-        else hipLaunchKernelGGL((irf_cols_kernel<T, V, N, BD>), grid, block, 0, p.stream, a);                          \
-    } while (0)
-            if (bounded) {
-                if (vec) {
-                    if (p.nt) VP_IRF_LAUNCH(true, true, true);
-                    else VP_IRF_LAUNCH(true, false, true);
-                } else {
-                    if (p.nt) VP_IRF_LAUNCH(false, true, true);
-                    else VP_IRF_LAUNCH(false, false, true);
-                }
-            } else if (vec) {
-                if (p.nt) VP_IRF_LAUNCH(true, true, false);
-                else VP_IRF_LAUNCH(true, false, false);
-            } else {
-                if (p.nt) VP_IRF_LAUNCH(false, true, false);
-                else VP_IRF_LAUNCH(false, false, false);
-            }
-#undef VP_IRF_LAUNCH
-            if (hipGetLastError() != hipSuccess) return VP_ERR_HIP;
-        }
+            select_variant(
+                [&](auto V, auto N, auto BD, auto PER) {
+                    if constexpr (PER.value) hipLaunchKernelGGL((irf_cols_periodic_kernel<T, V.value, N.value, BD.value>), grid, block, 0, p.stream, a, period);
+                    else hipLaunchKernelGGL((irf_cols_kernel<T, V.value, N.value, BD.value>), grid, block, 0, p.stream, a);
+                },
+                vec, p.nt != 0, bounded, periodic != 0);
+        });
+        if (rc) return rc;
     }
     return VP_ERR_OK;
 }
