@@ -99,6 +99,10 @@ extern "C" {
     pub fn vp_best_fit(h: *mut vp_batch, fit_out: *mut c_void) -> i32;
     /// parity diagnostics of the fp64-Gram fit kernel: {1/2||r||^2, c, J^T r, J^T J} at alpha, per problem
     pub fn vp_debug_gram_evaluate(h: *mut vp_batch, alpha: *const c_void, out: *mut f64) -> i32;
+    /// which compiled kernel set the handle runs on: {dtype, family, a, b, c, R, W, uses_gen_ws}
+    pub fn vp_debug_kernel_set(h: *mut vp_batch, out: *mut i32) -> i32;
+    /// the same record for entry `index` of the table of sets; 1 / 0: serves single-RHS handles or not, < 0 past the end
+    pub fn vp_debug_registry_entry(index: i32, out: *mut i32) -> i32;
     pub fn vp_summary(h: *mut vp_batch, out: *mut f64) -> i32;
     pub fn vp_summary_device(h: *mut vp_batch, dev_out4: *mut f64) -> i32;
     pub fn vp_global_fit_condition(h: *mut vp_batch, cond_out: *mut f64) -> i32;

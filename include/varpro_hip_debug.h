@@ -55,6 +55,24 @@ int vp_debug_set_column_fit(vp_batch *h, int look_every, int nontemporal);
  */
 int vp_debug_search_ms(vp_batch *h, float ms_out[4]);
 
+/*
+ * Which compiled kernel set a handle runs on (tests/stats_cases.py: every case names the set it is meant to reach).
+ * out = { dtype (VP_F64 / VP_F32), family, a, b, c, R, W, uses_gen_ws } of the handle's set:
+ *   family 1: multi-exponential, (a, b, c) = (exponentials, offset 0/1, 0);  family 2: run-time descriptor, (a, b, c) =
+ *   (basis functions, parameters, pairs);  family 3: the generic kernels (a = b = c = R = 0; caller-evaluated handles too);
+ *   R rows per lane, W waves per problem: the set holds m <= 64 R W;  uses_gen_ws = 1 with family 1 or 2: a
+ *   length-agnostic set (R = 2^20), whose statistics and best fit run on the generic kernels.
+ * A plain read: no GPU work, no state.
+ */
+int vp_debug_kernel_set(vp_batch *h, int32_t out[8]);
+
+/*
+ * The same record for entry `index` of the table of registered sets, without a handle and without a device.  Returns 1
+ * if the entry carries both an evaluation and a statistics kernel, i.e. a single-right-hand-side handle can land on it,
+ * 0 if it serves handles with several right-hand sides only, VP_ERR_INVALID past the end of the table.
+ */
+int vp_debug_registry_entry(int index, int32_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,7 +60,7 @@ ABI_SYMBOLS = [
 
 # test hooks (include/varpro_hip_debug.h): exported by the library, not part of the drop-in boundary
 DEBUG_SYMBOLS = ["vp_debug_gram_evaluate", "vp_debug_lmpar_gram", "vp_debug_set_refit", "vp_debug_set_column_fit",
-                 "vp_debug_search_ms"]
+                 "vp_debug_search_ms", "vp_debug_kernel_set", "vp_debug_registry_entry"]
 
 
 class VarproHipUnavailable(ImportError):
@@ -157,6 +157,9 @@ def load():
     lib.vp_debug_set_refit.argtypes = [vp, C.c_int]
     if hasattr(lib, "vp_debug_set_column_fit"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no such hook)
         lib.vp_debug_set_column_fit.argtypes = [vp, C.c_int, C.c_int]
+    if hasattr(lib, "vp_debug_kernel_set"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no such hooks)
+        lib.vp_debug_kernel_set.argtypes = [vp, i32p]
+        lib.vp_debug_registry_entry.argtypes = [C.c_int, i32p]
     lib.vp_statistics.argtypes = [vp, vp, vp, vp, vp]
     lib.vp_global_statistics.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.vp_summary.argtypes = [vp, dp]
@@ -185,3 +188,19 @@ def check(rc):
 
 def device_count():
     return load().vp_device_count()
+
+
+KERNEL_SET_FIELDS = ("dtype", "family", "a", "b", "c", "R", "W", "uses_gen_ws")
+FAMILY_MULTIEXP, FAMILY_RT, FAMILY_GENERIC = 1, 2, 3
+
+
+def registry_entries():
+    """test hook (vp_debug_registry_entry): the registered kernel sets as a list of (record, single_rhs) -- record the tuple
+    KERNEL_SET_FIELDS, single_rhs True if the set carries an evaluation and a statistics kernel.  Needs no GPU."""
+    lib = load()
+    out, rec = [], (C.c_int32 * 8)()
+    while True:
+        rc = lib.vp_debug_registry_entry(len(out), rec)
+        if rc < 0:
+            return out
+        out.append((tuple(int(v) for v in rec), rc == 1))

@@ -590,6 +590,13 @@ class BatchProblem:
         return dict(cost=out[:, 0], C=out[:, 1:1 + n], Jtr=out[:, 1 + n:1 + n + q],
                     JtJ=out[:, 1 + n + q:].reshape(self.B, q, q))
 
+    def kernel_set(self):
+        """test hook (vp_debug_kernel_set): the compiled kernel set this handle runs on, the tuple _lib.KERNEL_SET_FIELDS
+        = (dtype, family, a, b, c, R, W, uses_gen_ws)"""
+        rec = (C.c_int32 * 8)()
+        check(self.lib.vp_debug_kernel_set(self._h, rec))
+        return tuple(int(v) for v in rec)
+
     @_device_entry
     def best_fit(self):
         """== FitResult::best_fit (src/fit.rs:55-59, 87-91)"""

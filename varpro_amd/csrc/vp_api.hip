@@ -2322,6 +2322,26 @@ int vp_debug_set_column_fit(vp_batch *h, int look_every, int nontemporal) {
     return VP_ERR_OK;
 }
 
+static void kernel_set_record(const KernelEntry &e, int32_t out[8]) {
+    const int32_t rec[8] = {e.dtype, e.family, e.a, e.b, e.c, e.R, e.W, e.uses_gen_ws};
+    for (int i = 0; i < 8; ++i) out[i] = rec[i];
+}
+
+int vp_debug_kernel_set(vp_batch *h, int32_t out[8]) {
+    if (!h || !h->kern) return fail(VP_ERR_INVALID, "null handle");
+    if (!out) return fail(VP_ERR_INVALID, "null out");
+    kernel_set_record(*h->kern, out);
+    return VP_ERR_OK;
+}
+
+int vp_debug_registry_entry(int index, int32_t out[8]) {
+    if (!out) return fail(VP_ERR_INVALID, "null out");
+    if (index < 0 || (size_t)index >= registry().size()) return fail(VP_ERR_INVALID, "no such registry entry");
+    const KernelEntry &e = registry()[(size_t)index];
+    kernel_set_record(e, out);
+    return e.stats && e.evaluate ? 1 : 0;
+}
+
 int vp_debug_set_refit(vp_batch *h, int enabled) {
     VP_ENTER(h);
     h->rescue_off = enabled == 0;
@@ -2750,8 +2770,10 @@ const KernelEntry *find_kernels(int dtype, const vp_model_desc &d, int64_t m, in
     const int fam = classify_model(d, a, b, c, p);
     if (fam < 0) return nullptr;
     const KernelEntry *best = nullptr;
-    for (int pass = 0; pass < 2 && !best; ++pass) {
-        // pass 0: exact family; pass 1: a multi-exponential model may also run on the runtime-model kernels
+    // pass 0: exact family; pass 1: a multi-exponential model may also run on the runtime-model kernels -- where its own
+    // family has no set for m, and also where it only has the length-agnostic one: that set loses against every resident set
+    // that covers m (vp_inst_blk.hpp), whichever family registered it (triple exponential without offset at 128 < m <= 1024)
+    for (int pass = 0; pass < 2 && (!best || best->uses_gen_ws); ++pass) {
         int f = fam, ka = a, kb = b, kc = c;
         if (pass == 1) {
             if (fam != FAMILY_MULTIEXP) break;
