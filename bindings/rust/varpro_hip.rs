@@ -64,6 +64,9 @@ pub const VP_FLAG_NO_GRID_RECURRENCE: i32 = 16;
 pub const VP_FLAG_DEVICE_COLUMNS: i32 = 64;
 /// `vp_search`: the candidates are `[B][K][q]`, one set per problem
 pub const VP_SEARCH_PER_PROBLEM: i32 = 1;
+/// `vp_poisson_reweight`: variance = max(count, floor) / max(best fit, floor)
+pub const VP_POISSON_NEYMAN: i32 = 0;
+pub const VP_POISSON_MODEL: i32 = 1;
 
 #[link(name = "varpro_hip")]
 extern "C" {
@@ -78,6 +81,13 @@ extern "C" {
     pub fn vp_linear_coeffs(h: *mut vp_batch, c_out: *mut c_void, status: *mut i32) -> i32;
     pub fn vp_weighted_data(h: *mut vp_batch, yw_out: *mut c_void) -> i32;
     pub fn vp_set_observations(h: *mut vp_batch, y: *const c_void) -> i32;
+    /// replace the weights of a handle created with weights (`[m]`, or `[B][m]` with `VP_FLAG_W_PER_PROBLEM`); `y` again,
+    /// because the handle keeps only `W Y`
+    pub fn vp_set_weights(h: *mut vp_batch, w: *const c_void, y: *const c_void) -> i32;
+    /// Poisson weights formed on the device from the counts `y` (`VP_POISSON_NEYMAN`) or from the handle's best fit
+    /// (`VP_POISSON_MODEL`: `deviance_out` / `pearson_out` `[B]` f64 or null); S = 1, per-problem weights
+    pub fn vp_poisson_reweight(h: *mut vp_batch, y: *const c_void, mode: i32, floor: f64, deviance_out: *mut f64,
+        pearson_out: *mut f64) -> i32;
     /// box bounds of `vp_fit` on a device-column handle: host doubles `[q]` or `[B][q]`, infinite = unbounded, both null clears
     pub fn vp_set_bounds(h: *mut vp_batch, lower: *const f64, upper: *const f64, per_problem: i32) -> i32;
     /// instrument response of a handle whose descriptor has an IRF kind: `[m]` or `[B][m]` in the handle's dtype and address

@@ -328,6 +328,62 @@ int vp_weighted_data(vp_batch *h, void *Yw_out);
  */
 int vp_set_observations(vp_batch *h, const void *Y);
 
+/*
+ * Replace the weights of a handle that was CREATED WITH weights (same B, S, m, model and grid).  w has the layout fixed at
+ * creation -- [m], or [B][m] with VP_FLAG_W_PER_PROBLEM -- and the handle's dtype and address space.  Y [B][S][m] must be
+ * passed again: the handle keeps only Y_w = W*Y (vp_batch_create), not Y, so the new weighted data can only be formed from
+ * the caller's observations.  Every cached evaluation / fit is invalidated, as by vp_set_observations; afterwards the handle
+ * is, bit for bit, the handle vp_batch_create would have made with these weights.  Any S and every handle kind (in-register,
+ * device-column, caller-evaluated) is accepted.  Device-pointer handles stay asynchronous (one copy, one launch).
+ * VP_ERR_INVALID: a null pointer, a stepped fit in progress, a handle created without weights (w == NULL selected the
+ * kernel set of Weights::Unit at creation; such a handle cannot take weights later).  VP_ERR_UNSUPPORTED: a handle padded
+ * for m < n.  A refusal leaves the handle as it was.
+ */
+int vp_set_weights(vp_batch *h, const void *w, const void *Y);
+
+/*
+ * Poisson-weighted fits.  Photon counts y_i are Poisson with mean f_i, so the weight of a least-squares fit is
+ * w_i = 1/sqrt(variance_i).  vp_poisson_reweight forms the weights ON THE DEVICE, replaces the handle's weights and its
+ * weighted data by them -- one pass (vp_poisson.hpp) -- and the next vp_fit uses them:
+ *   VP_POISSON_NEYMAN   variance = max(y_i, floor)   from the counts Y alone ("Neyman" weighting)
+ *   VP_POISSON_MODEL    variance = max(f_i, floor)   from the handle's current best fit f = Phi(alpha) c, UNWEIGHTED, as
+ *                       vp_best_fit returns it ("Pearson" / model weighting), evaluated into a [B][m] scratch buffer the
+ *                       handle owns (allocated at the first call).  Needs parameters (after vp_fit, vp_set_params,
+ *                       vp_evaluate, vp_search or -- caller-evaluated handles -- vp_set_params_with_basis, whose columns
+ *                       must still be valid).  Works on in-register, device-column and caller-evaluated handles.
+ *   w_i = 1/sqrt(variance_i),  Y_w,i = w_i y_i       floor > 0 keeps empty bins finite; 1 is customary
+ *   deviance_out [B] f64   D   = 2 sum_i [ y_i ln(y_i/ft_i) - (y_i - ft_i) ],  ft = max(f, floor); the logarithmic term is 0
+ *                              for y_i <= 0: the Poisson deviance, the goodness-of-fit number of a likelihood fit
+ *   pearson_out  [B] f64   X^2 = sum_i (y_i - ft_i)^2 / ft_i
+ *                          both of the fit the weights were formed FROM, accumulated in double for both dtypes in a fixed
+ *                          order; they follow the handle's address space, either may be NULL, and both MUST be NULL in Neyman
+ *                          mode (there is no fit to judge).
+ * A fit with w = 1/sqrt(f) held fixed, f re-formed from the result and the fit repeated from the previous parameters has as
+ * its fixed point the Poisson score equations sum_i (y_i - f_i)/f_i df_i/dtheta = 0: iterating {vp_poisson_reweight(MODEL),
+ * vp_fit} IS the Poisson maximum-likelihood fit (the first round weighted by VP_POISSON_NEYMAN).  A fixed number of rounds
+ * keeps a device-pointer pipeline free of host visits (measured: DESIGN.md section 3i).
+ * A problem whose status is non-zero in model mode (its evaluation failed, there is no fit) keeps its weights and weighted
+ * data and gets NaN in both sums: a failed round does not poison the next one.  A non-finite count or fit value gives a
+ * non-finite weight, and the next evaluation latches the problem like any other non-finite input.
+ * Afterwards every cached evaluation is invalidated (the residuals belong to the old weights); vp_params still returns the
+ * parameters, so that the next vp_fit can start from them.  Device-pointer handles stay asynchronous, except for the one
+ * allocation of the scratch buffer at the first model-mode call.
+ * To know:
+ *   - vp_statistics after the last round is the statistics of the WEIGHTED LEAST-SQUARES problem at the final weights: with
+ *     w = 1/sqrt(f) that is the Fisher-information covariance at the maximum-likelihood estimate, the usual one; its
+ *     reduced chi^2 is Pearson's X^2 / (m - n - q) at the weights of the previous round, not the deviance;
+ *   - bounds (vp_set_bounds), vp_search and vp_set_irf compose unchanged: they act on the fit, not on the weights;
+ *   - weights are per problem, not per right-hand side: S = 1 only; this is iterated re-weighting, not an LM on deviance
+ *     residuals; m < n is not covered.
+ * VP_ERR_INVALID: a null Y, an unknown mode, a floor that is not finite and > 0, outputs passed in Neyman mode, a stepped fit
+ * in progress, a handle not created with VP_FLAG_W_PER_PROBLEM and a weights array, model mode before any parameters are set
+ * and -- caller-evaluated handles -- model mode without columns at the current parameters.  VP_ERR_UNSUPPORTED: S > 1, a
+ * handle padded for m < n.  A refusal leaves the handle as it was.
+ */
+enum { VP_POISSON_NEYMAN = 0, VP_POISSON_MODEL = 1 };
+int vp_poisson_reweight(vp_batch *h, const void *Y, int mode, double floor,
+                        double *deviance_out, double *pearson_out);
+
 /* Box bounds on the nonlinear parameters of vp_fit, device-column handles only (see "device-column handles" above).
  * lower / upper: HOST pointers to doubles whatever the handle's dtype and flags, [q] (per_problem = 0) or [B][q];
  * -INFINITY / +INFINITY = unbounded on that side; both NULL clears the bounds.  Stays set across vp_fit calls and

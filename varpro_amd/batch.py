@@ -30,6 +30,9 @@ REPORT_DTYPE = np.dtype([("termination", np.int32), ("n_evals", np.int32), ("obj
 
 STATUS_OK, STATUS_NONFINITE, STATUS_NOT_EVALUATED = 0, 1, 2
 
+# fit_poisson: model-weighted rounds after the Neyman fit (measured on the CPU mirror)
+POISSON_ROUNDS = 9
+
 
 def _is_torch(a):
     return torch is not None and isinstance(a, torch.Tensor)
@@ -190,6 +193,14 @@ class BatchProblem:
             # SeparableProblemBuilderError::InvalidLengthOfData (src/problem/builder.rs:294-299)
             raise ValueError("InvalidLengthOfData: x length = %d and y length = %d" % (int(x.shape[0]), self.m))
         w = None
+        if isinstance(weights, str):
+            # Neyman weights of Poisson counts, w = 1/sqrt(max(y, 1)) per problem, formed where the data lives
+            if weights != "neyman":
+                raise ValueError("weights: an array, None or \"neyman\"")
+            if not self.single_rhs:
+                raise ValueError("weights=\"neyman\": weights are per problem, not per right-hand side (S = 1 only)")
+            one = Y.new_ones(()) if self.device_mode else self.np_dtype.type(1)
+            weights = 1.0 / (torch.sqrt(torch.maximum(Y, one)) if self.device_mode else np.sqrt(np.maximum(Y, one)))
         if weights is not None:
             w = self._as_array(weights)
             if w.ndim == 2:
@@ -198,6 +209,8 @@ class BatchProblem:
                     raise ValueError("InvalidLengthOfWeights")
             elif int(w.shape[0]) != self.m:
                 raise ValueError("InvalidLengthOfWeights")  # src/problem/builder.rs:300-303
+        self.weighted = w is not None                     # set_weights needs a handle created with weights,
+        self.w_per_problem = w is not None and w.ndim == 2  # poisson_reweight one with weights per problem
         self.irf_kinds = (not self.external) and any(k in _basis.IRF_KINDS for k in model.kinds)
         if irf is not None:
             if not self.irf_kinds:
@@ -646,6 +659,82 @@ class BatchProblem:
             Y = Y.contiguous()
         check(self.lib.vp_set_observations(self._h, self._ptr(Y)))
         self._have_params = False
+
+    # ---- weights between fits; Poisson-weighted fits (vp_set_weights, vp_poisson_reweight) ----
+    def _checked_observations(self, Y, what):
+        Y = self._as_array(Y)
+        want = (self.B, self.m) if self.single_rhs else (self.B, self.S, self.m)
+        if tuple(Y.shape) != want:
+            raise ValueError("%s: observations must have shape %r" % (what, want))
+        return Y
+
+    @_device_entry
+    def set_weights(self, w, Y):
+        """replace the weights of a handle that was created with weights (vp_set_weights): w in the layout of creation,
+        (m,) or (B, m); Y the observations again -- the handle keeps only W Y, so the new weighted data is formed from
+        them.  Cached results are invalidated, as by ``set_observations``."""
+        if not self.weighted:
+            raise ValueError("set_weights: the handle was created without weights (unit-weight handles run on other kernels)")
+        w = self._as_array(w)
+        if tuple(w.shape) != ((self.B, self.m) if self.w_per_problem else (self.m,)):
+            raise ValueError("set_weights: the weights keep the layout of creation, %s"
+                             % ("(B, m)" if self.w_per_problem else "(m,)"))
+        Y = self._checked_observations(Y, "set_weights")
+        check(self.lib.vp_set_weights(self._h, self._ptr(w), self._ptr(Y)))
+        self._have_params = False
+
+    @_device_entry
+    def poisson_reweight(self, Y, mode="model", floor=1.0):
+        """Weights of Poisson counts Y (B, m), formed on the device (vp_poisson_reweight): w = 1/sqrt(max(v, floor)) with
+        v = Y (mode "neyman") or v = the handle's current best fit (mode "model": after ``fit`` / ``set_params``).  The
+        handle's weights and weighted data are replaced, cached results are invalidated, ``params()`` still returns the
+        parameters.  "model" returns ``(deviance, pearson)``, both (B,) float64 -- the Poisson deviance
+        2 sum [y ln(y/f) - (y - f)] and Pearson's X^2 = sum (y - f)^2 / f of the fit the weights were formed from (NaN for a
+        problem whose evaluation failed; its weights are kept) -- and "neyman" returns None.  Needs a single right-hand
+        side and a handle created with per-problem weights (``weights="neyman"`` or a (B, m) array)."""
+        if mode not in ("neyman", "model"):
+            raise ValueError("poisson_reweight: mode is \"neyman\" or \"model\"")
+        floor = float(floor)
+        if not (np.isfinite(floor) and floor > 0.0):
+            raise ValueError("poisson_reweight: the floor must be finite and > 0")
+        if not self.single_rhs:
+            raise ValueError("poisson_reweight: weights are per problem, not per right-hand side (S = 1 only)")
+        if not self.w_per_problem:
+            raise ValueError("poisson_reweight: the handle needs per-problem weights (weights=\"neyman\" or a (B, m) array)")
+        Y = self._checked_observations(Y, "poisson_reweight")
+        if mode == "model" and not self._have_params:
+            raise ValueError("poisson_reweight: mode \"model\" needs the fit of the current parameters (fit / set_params first)")
+        dev = pear = None
+        if mode == "model":
+            dev, pear = self._empty((self.B,), np.float64), self._empty((self.B,), np.float64)
+        check(self.lib.vp_poisson_reweight(self._h, self._ptr(Y), _lib.VP_POISSON_MODEL if mode == "model" else
+                                           _lib.VP_POISSON_NEYMAN, C.c_double(floor), self._ptr(dev), self._ptr(pear)))
+        self._have_params = False
+        return (dev, pear) if mode == "model" else None
+
+    def fit_poisson(self, counts, alpha0, rounds=POISSON_ROUNDS, floor=1.0, solver=None):
+        """Poisson maximum-likelihood fit of counts (B, m) by iterated re-weighting: a Neyman-weighted fit from alpha0, then
+        ``rounds`` fits with the weights 1/sqrt(max(f, floor)) of the previous fit, each from the previous parameters -- the
+        fixed point of which is the Poisson score equations.  One more model re-weight and an evaluation end it, so the
+        returned ``(alpha, C, report, info)`` carries ``info = dict(deviance, pearson, reduced_deviance, rounds)`` AT the
+        returned point and the handle's state is that point (``statistics()``, ``best_fit()`` need no further call; the
+        statistics are those of the weighted least-squares problem at the final weights, i.e. the Fisher-information
+        covariance at the estimate).  report is the last fit's.  ``rounds`` is a fixed count: a device-pointer handle makes
+        no host visit between the rounds."""
+        rounds = int(rounds)
+        if rounds < 0:
+            raise ValueError("fit_poisson: rounds >= 0")
+        self.poisson_reweight(counts, "neyman", floor)
+        a, Cm, rep = self.fit(alpha0, solver)
+        for _ in range(rounds):
+            self.poisson_reweight(counts, "model", floor)
+            a, Cm, rep = self.fit(a, solver)
+        # deviance and X^2 of the returned (alpha, C); the evaluation makes the handle's state that alpha at the final weights
+        # (its coefficients differ from C by what one more round would change: nothing beyond the fits' own stopping noise)
+        dev, pear = self.poisson_reweight(counts, "model", floor)
+        self.evaluate(a, want_residuals=False, want_jacobian=False)
+        info = dict(deviance=dev, pearson=pear, reduced_deviance=dev / float(self.m - self.n - self.q), rounds=rounds)
+        return a, Cm, rep, info
 
     @_device_entry
     def set_irf(self, irf):

@@ -293,6 +293,7 @@ inline double student_t_quantile(double p, double dof) {
 // B independent problems x S right-hand sides on one GPU (host-pointer mode; fp64)
 class BatchProblem {
     vp_batch *h_ = nullptr;
+    bool weighted_ = false, w_per_problem_ = false; // created with weights / with one set per problem
 
   public:
     int64_t m = 0, S = 1, B = 0;
@@ -307,8 +308,19 @@ class BatchProblem {
         n = model.desc.n_basis;
         q = model.desc.n_params;
         if ((int64_t)Y.size() != B * S * m) throw std::invalid_argument("Y must hold B*S*m values");
+        // weights: m values shared by the batch, or B*m values, one set per problem (what poisson_reweight needs)
+        weighted_ = weights != nullptr;
+        w_per_problem_ = weights && (int64_t)weights->size() == B * m && B > 1;
+        if (weights && (int64_t)weights->size() != m && !w_per_problem_) throw std::invalid_argument("weights must hold m or B*m values");
         check(vp_batch_create(&h_, &model.desc, VP_F64, m, S, B, model.x.data(), Y.data(), weights ? weights->data() : nullptr,
-                              epsilon, VP_FLAG_OWN_STREAM | (device_columns ? VP_FLAG_DEVICE_COLUMNS : 0), device, nullptr));
+                              epsilon, VP_FLAG_OWN_STREAM | (device_columns ? VP_FLAG_DEVICE_COLUMNS : 0) |
+                                           (w_per_problem_ ? VP_FLAG_W_PER_PROBLEM : 0), device, nullptr));
+    }
+    // Neyman weights of Poisson counts, w = 1/sqrt(max(y, 1)): the `weights` of a handle that fit_poisson will drive
+    static std::vector<double> neyman_weights(const std::vector<double> &counts) {
+        std::vector<double> w(counts.size());
+        for (size_t i = 0; i < counts.size(); ++i) w[i] = 1.0 / std::sqrt(counts[i] < 1.0 ? 1.0 : counts[i]);
+        return w;
     }
     BatchProblem(const BatchProblem &) = delete;
     BatchProblem &operator=(const BatchProblem &) = delete;
@@ -316,6 +328,7 @@ class BatchProblem {
     BatchProblem &operator=(BatchProblem &&o) noexcept {
         std::swap(h_, o.h_);
         m = o.m, S = o.S, B = o.B, n = o.n, q = o.q;
+        weighted_ = o.weighted_, w_per_problem_ = o.w_per_problem_;
         return *this;
     }
     ~BatchProblem() {
@@ -327,6 +340,63 @@ class BatchProblem {
     void set_observations(const std::vector<double> &Y) {
         if ((int64_t)Y.size() != B * S * m) throw std::invalid_argument("Y must hold B*S*m values");
         check(vp_set_observations(h_, Y.data()));
+    }
+    // replace the weights of a handle created with weights, in the layout of creation (vp_set_weights); Y again: the handle
+    // keeps only W Y
+    void set_weights(const std::vector<double> &w, const std::vector<double> &Y) {
+        if (!weighted_) throw std::invalid_argument("set_weights: the handle was created without weights");
+        if ((int64_t)w.size() != (w_per_problem_ ? B * m : m)) throw std::invalid_argument("set_weights: the weights keep the layout of creation");
+        if ((int64_t)Y.size() != B * S * m) throw std::invalid_argument("Y must hold B*S*m values");
+        check(vp_set_weights(h_, w.data(), Y.data()));
+    }
+    // Poisson weights formed on the device (vp_poisson_reweight): 1/sqrt(max(v, floor)), v = the counts (VP_POISSON_NEYMAN) or
+    // the handle's current best fit (VP_POISSON_MODEL, which also returns the deviance and Pearson's X^2 of that fit, [B] each)
+    struct PoissonGoodness {
+        std::vector<double> deviance, pearson;
+    };
+    PoissonGoodness poisson_reweight(const std::vector<double> &counts, int mode = VP_POISSON_MODEL, double floor = 1.0) {
+        if (mode != VP_POISSON_NEYMAN && mode != VP_POISSON_MODEL) throw std::invalid_argument("poisson_reweight: unknown mode");
+        if (!(floor > 0.0) || !std::isfinite(floor)) throw std::invalid_argument("poisson_reweight: the floor must be finite and > 0");
+        if (S != 1) throw std::invalid_argument("poisson_reweight: weights are per problem, not per right-hand side (S = 1 only)");
+        if (!w_per_problem_) throw std::invalid_argument("poisson_reweight: the handle needs per-problem weights (B*m values)");
+        if ((int64_t)counts.size() != B * m) throw std::invalid_argument("counts must hold B*m values");
+        PoissonGoodness g;
+        if (mode == VP_POISSON_MODEL) g.deviance.resize((size_t)B), g.pearson.resize((size_t)B);
+        check(vp_poisson_reweight(h_, counts.data(), mode, floor, mode == VP_POISSON_MODEL ? g.deviance.data() : nullptr,
+                                  mode == VP_POISSON_MODEL ? g.pearson.data() : nullptr));
+        return g;
+    }
+    // Poisson maximum-likelihood fit by iterated re-weighting (== the Python BatchProblem.fit_poisson): a Neyman-weighted fit
+    // from alpha0, `rounds` fits at the weights of the previous fit, one more model re-weight and an evaluation -- the
+    // result carries deviance, Pearson's X^2 and the reduced deviance D / (m - n - q) AT the returned point, which is the
+    // handle's state (statistics(), best_fit() need no further call).  The default `rounds` is measured: DESIGN.md section 3i
+    struct PoissonFit {
+        std::vector<double> alpha, C; // [B][q], [B][n]
+        std::vector<vp_report> report; // the last fit's
+        std::vector<double> deviance, pearson, reduced_deviance; // [B]
+    };
+    static constexpr int kPoissonRounds = 9;
+    PoissonFit fit_poisson(const std::vector<double> &counts, const std::vector<double> &alpha0, int rounds = kPoissonRounds,
+                           double floor = 1.0, const LevenbergMarquardt &solver = LevenbergMarquardt()) {
+        if (rounds < 0) throw std::invalid_argument("fit_poisson: rounds >= 0");
+        PoissonFit r;
+        r.alpha = alpha0;
+        r.report.resize((size_t)B);
+        r.C.resize((size_t)(B * n));
+        poisson_reweight(counts, VP_POISSON_NEYMAN, floor);
+        check(vp_fit(h_, &solver.o, r.alpha.data(), r.C.data(), r.report.data()));
+        for (int k = 0; k < rounds; ++k) {
+            poisson_reweight(counts, VP_POISSON_MODEL, floor);
+            check(vp_fit(h_, &solver.o, r.alpha.data(), r.C.data(), r.report.data()));
+        }
+        // deviance and X^2 of the returned (alpha, C); the evaluation makes the handle's state that alpha at the final weights
+        PoissonGoodness g = poisson_reweight(counts, VP_POISSON_MODEL, floor);
+        check(vp_evaluate(h_, r.alpha.data(), nullptr, nullptr, nullptr, nullptr, nullptr));
+        r.reduced_deviance.resize((size_t)B);
+        for (int64_t b = 0; b < B; ++b) r.reduced_deviance[(size_t)b] = g.deviance[(size_t)b] / (double)(m - n - q);
+        r.deviance = std::move(g.deviance);
+        r.pearson = std::move(g.pearson);
+        return r;
     }
     // box bounds of fit() on a device-column handle (vp_set_bounds): q values (one box for all problems) or B*q values
     // each; +-INFINITY = unbounded on that side.  The bounds stay set until clear_bounds()

@@ -20,6 +20,7 @@
 #include "vp_gstats.hpp"
 #include "vp_cols.hpp"
 #include "vp_search.hpp"
+#include "vp_poisson.hpp"
 
 using namespace vp;
 
@@ -296,6 +297,8 @@ struct __attribute__((visibility("hidden"))) vp_batch {
     bool have_params = false;  // set_params/evaluate/fit has run
     bool r_valid = false;      // d_R matches d_alpha
     bool have_report = false;
+    bool alpha_kept = false;   // vp_poisson_reweight: the evaluation is gone, d_alpha still holds the parameters (vp_params)
+    void *d_pfit = nullptr;    // vp_poisson_reweight, model mode: [B][m] best fit the weights are formed from; at first use
     // timing
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -716,6 +719,7 @@ void invalidate(vp_batch *h) {
     h->have_params = false;
     h->r_valid = false;
     h->have_report = false;
+    h->alpha_kept = false;
 }
 
 // a fit's results into the caller's arrays (each may be null)
@@ -1750,7 +1754,7 @@ int vp_set_params(vp_batch *h, const void *alpha) {
 
 int vp_params(vp_batch *h, void *alpha_out) {
     VP_ENTER(h);
-    if (!h->have_params) return fail(VP_ERR_INVALID, "no parameters set yet");
+    if (!h->have_params && !h->alpha_kept) return fail(VP_ERR_INVALID, "no parameters set yet");
     return copy_out(h, alpha_out, h->d_alpha, (size_t)h->B * h->q * tsize(h->dtype));
 }
 
@@ -2450,19 +2454,107 @@ int vp_set_rhs_allreduce(vp_batch *h, vp_allreduce_fn fn, void *user, int64_t gl
     return VP_ERR_OK;
 }
 
+// UNWEIGHTED Phi(alpha) * C of the handle's current parameters into fit_dev [B][S][m] (device memory)
+static int launch_best_fit(vp_batch *h, void *fit_dev) {
+    LaunchParams p;
+    fill_params(h, p);
+    p.C_out = h->d_C; // input here
+    p.r_out = fit_dev; // output
+    int rc = h->kern->best_fit(p);
+    if (rc != VP_ERR_OK) return fail(rc, "best_fit kernel launch failed");
+    return VP_ERR_OK;
+}
+
 int vp_best_fit(vp_batch *h, void *fit_out) {
     VP_ENTER(h);
     if (!h->have_params) return fail(VP_ERR_INVALID, "no parameters set yet");
     if (!h->kern->best_fit) return fail(VP_ERR_UNSUPPORTED, "no best_fit kernel for this model");
     RowOut f;
     if (int rc = f.init(h, fit_out, (size_t)h->B * h->S)) return rc;
-    LaunchParams p;
-    fill_params(h, p);
-    p.C_out = h->d_C; // input here
-    p.r_out = f.dptr; // output
-    int rc = h->kern->best_fit(p);
-    if (rc != VP_ERR_OK) return fail(rc, "best_fit kernel launch failed");
+    if (int rc = launch_best_fit(h, f.dptr)) return rc;
     return f.finish(h);
+}
+
+// ---- weights between fits (vp_set_weights) and Poisson re-weighting on the device (vp_poisson.hpp) --------------------------
+int vp_set_weights(vp_batch *h, const void *w, const void *Y) {
+    VP_ENTER(h);
+    if (!w || !Y) return fail(VP_ERR_INVALID, "vp_set_weights: null w or Y (the handle keeps only W*Y: pass the observations again)");
+    if (!h->d_w)
+        return fail(VP_ERR_INVALID, "vp_set_weights: the handle was created without weights (its kernel set is the one of unit "
+                                    "weights); create it with a weights array");
+    if (h->xf_running) return fail(VP_ERR_INVALID, "vp_set_weights during a stepped fit");
+    if (h->m_user) return fail(VP_ERR_UNSUPPORTED, "vp_set_weights: not available on a handle padded for m < n");
+    const size_t ts = tsize(h->dtype);
+    const size_t w_elems = (size_t)((h->flags & VP_FLAG_W_PER_PROBLEM) ? h->B * h->m : h->m);
+    const size_t y_elems = (size_t)h->B * h->S * h->m;
+    const hipMemcpyKind kin = device_ptrs(h) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    VP_HIP(hipMemcpyAsync(h->d_w, w, w_elems * ts, kin, h->stream));
+    // Y_w = W * Y as vp_set_observations forms it: host data is staged through the handle's buffer and weighted in place
+    const void *ysrc = Y;
+    if (!device_ptrs(h)) {
+        VP_HIP(hipMemcpyAsync(h->d_yw, Y, y_elems * ts, hipMemcpyHostToDevice, h->stream));
+        ysrc = h->d_yw;
+    }
+    if (int rc = launch_weight_data(h, ysrc)) return rc;
+    if (!device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream)); // the caller may reuse its host buffers
+    invalidate(h); // the cached evaluation / fit belongs to the old weights
+    return VP_ERR_OK;
+}
+
+int vp_poisson_reweight(vp_batch *h, const void *Y, int mode, double floor, double *deviance_out, double *pearson_out) {
+    VP_ENTER(h);
+    if (!Y) return fail(VP_ERR_INVALID, "vp_poisson_reweight: null Y");
+    if (mode != VP_POISSON_NEYMAN && mode != VP_POISSON_MODEL) return fail(VP_ERR_INVALID, "vp_poisson_reweight: unknown mode");
+    if (!(floor > 0.0) || !std::isfinite(floor)) return fail(VP_ERR_INVALID, "vp_poisson_reweight: the floor must be finite and > 0");
+    const bool model = mode == VP_POISSON_MODEL;
+    if (!model && (deviance_out || pearson_out))
+        return fail(VP_ERR_INVALID, "vp_poisson_reweight: deviance and Pearson X^2 belong to a fit; both outputs must be NULL in "
+                                    "Neyman mode");
+    if (h->xf_running) return fail(VP_ERR_INVALID, "vp_poisson_reweight during a stepped fit");
+    if (!h->d_w || !(h->flags & VP_FLAG_W_PER_PROBLEM))
+        return fail(VP_ERR_INVALID, "vp_poisson_reweight: the handle must be created with VP_FLAG_W_PER_PROBLEM and a weights array");
+    if (h->S != 1)
+        return fail(VP_ERR_UNSUPPORTED, "vp_poisson_reweight: weights are per problem, not per right-hand side (S = 1 only)");
+    if (h->m_user) return fail(VP_ERR_UNSUPPORTED, "vp_poisson_reweight: not available on a handle padded for m < n");
+    if (model) {
+        if (!h->have_params) return fail(VP_ERR_INVALID, "vp_poisson_reweight: model mode needs the fit of the current parameters (no parameters set yet)");
+        if (h->external && !h->ext_phi)
+            return fail(VP_ERR_INVALID, "vp_poisson_reweight: model mode needs the columns of the handle's current parameters "
+                                        "(vp_set_params_with_basis at the fitted parameters first)");
+        if (!h->kern->best_fit) return fail(VP_ERR_UNSUPPORTED, "no best_fit kernel for this model");
+    }
+    const size_t bytes = (size_t)h->B * h->m * tsize(h->dtype);
+    InBuf y;
+    OutBuf dev, pear;
+    if (int rc = y.init(h, Y, bytes)) return rc;
+    if (int rc = dev.init(h, deviance_out, (size_t)h->B * sizeof(double))) return rc;
+    if (int rc = pear.init(h, pearson_out, (size_t)h->B * sizeof(double))) return rc;
+    if (model) {
+        if (int rc = h->ensure(h->d_pfit, bytes)) return rc;
+        if (int rc = launch_best_fit(h, h->d_pfit)) return rc;
+    }
+    PoissonParams p;
+    p.dtype = h->dtype;
+    p.Y = y.dptr;
+    p.F = model ? h->d_pfit : nullptr;
+    p.status = h->d_status;
+    p.w = h->d_w;
+    p.yw = h->d_yw;
+    p.deviance = (double *)dev.dptr;
+    p.pearson = (double *)pear.dptr;
+    p.floor = floor;
+    p.m = (int)h->m;
+    p.B = h->B;
+    p.stream = h->stream;
+    if (int rc = poisson_reweight_launch(p)) return fail(rc, "Poisson re-weighting kernel launch failed");
+    // the cached evaluation belongs to the old weights; the parameters stay (vp_params), the next vp_fit can start from them
+    const bool had_alpha = h->have_params || h->alpha_kept;
+    invalidate(h);
+    h->alpha_kept = had_alpha;
+    if (int rc = dev.finish(h)) return rc;
+    if (int rc = pear.finish(h)) return rc;
+    if (!device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream)); // the staged counts go out of scope
+    return VP_ERR_OK;
 }
 
 int vp_statistics(vp_batch *h, void *cov_out, double *reduced_chi2_out, void *conf_sigma_out, int32_t *status) {
