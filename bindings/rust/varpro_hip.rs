@@ -113,6 +113,8 @@ extern "C" {
     pub fn vp_debug_kernel_set(h: *mut vp_batch, out: *mut i32) -> i32;
     /// the same record for entry `index` of the table of sets; 1 / 0: serves single-RHS handles or not, < 0 past the end
     pub fn vp_debug_registry_entry(index: i32, out: *mut i32) -> i32;
+    /// which fit kernel the last fit launched: {kernel 0..5, padding variant 1 / 2 / 0 / -1, weighted, 0}
+    pub fn vp_debug_last_fit(h: *mut vp_batch, out: *mut i32) -> i32;
     pub fn vp_summary(h: *mut vp_batch, out: *mut f64) -> i32;
     pub fn vp_summary_device(h: *mut vp_batch, dev_out4: *mut f64) -> i32;
     pub fn vp_global_fit_condition(h: *mut vp_batch, cond_out: *mut f64) -> i32;

@@ -73,6 +73,19 @@ int vp_debug_kernel_set(vp_batch *h, int32_t out[8]);
  */
 int vp_debug_registry_entry(int index, int32_t out[8]);
 
+/*
+ * Which fit kernel the handle's last single-right-hand-side vp_fit / vp_fit_trace launched, written by the launcher that
+ * issued the launch (so a slot-kernel launcher that hands the batch to the wave kernel reports the wave kernel):
+ * out = { kernel, padding, weighted, 0 }
+ *   kernel    0 = no fit yet, 1 = wave (one problem per wave group, vp_fit.hpp), 2 = slots (vp_fit2.hpp), 3 = Gram
+ *             (vp_fitg.hpp: fp32 handle, fp64 Gram matrix), 4 = row-block / length-agnostic (vp_block.hpp), 5 = generic
+ *   padding   the instantiation by length: 1 = m == 64 R W, 2 = m reaches the last register pair, 0 = general,
+ *             -1 = not applicable (kernels 3, 4, 5)
+ *   weighted  1 = the weighted instantiation (the Gram kernel's also masks a ragged last row group through the weights)
+ * The re-fit of flagged problems is not recorded.  A plain read: no GPU work, no state.
+ */
+int vp_debug_last_fit(vp_batch *h, int32_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,9 @@ SHAPES.update({
     # five exponentials a factor 4 apart on 0 .. 150: the fit case (at a factor 3.2 and noise 1e-3 one of the oracle's five
     # fits lets its longest decay time run off to 3e7, where H is singular to working precision)
     "me5o_wide": Shape([_E] * 5 + [_C], [(j,) for j in range(5)] + [()], [0.2, 0.8, 3.2, 12.8, 51.2], 150.0),
+    # three exponentials a factor 4 apart on 0 .. 25: the fit cases of tests/fit_cases.py (at 0.7, 2, 6 on 0 .. 12.5 the minimum of
+    # the oracle's own fit has kappa_s 1e4 .. 7e14 on five of the sizes there)
+    "me3o_wide": Shape([_E] * 3 + [_C], [(0,), (1,), (2,), ()], [0.5, 2.0, 8.0], 25.0),
     # no set has this shape (q = 5): the generic kernels
     "mixed5": Shape([_E, _X, _S, _C], [(0,), (1, 2), (3, 4), ()], [1.5, 0.25, 2.0, 0.9, 0.4], 12.5),
 })
@@ -123,17 +126,26 @@ def make_model(shape, x, dtype):
 
 
 # ---- the table -------------------------------------------------------------------------------------------------------------
-# weights: None, "shared" (m,) or "per" (B, m); grid: "shared" (m,) or "per" (B, m); stream: stream_rows=True
-Case = collections.namedtuple("Case", "shape dtype m set weights grid stream noise")
+# weights: None, "shared" (m,) or "per" (B, m); grid: "shared" (m,) or "per" (B, m); stream: stream_rows=True; uniform: the
+# shared grid is np.linspace (True, every case of this file) or a jittered one the library's grid check rejects (False,
+# tests/fit_cases.py; a per-problem grid is non-uniform whatever the flag says)
+Case = collections.namedtuple("Case", "shape dtype m set weights grid stream noise uniform")
 
 
-def case(shape, dtype, m, kset, weights=None, grid="shared", stream=False, noise=NOISE):
-    return Case(shape, dtype, m, kset, weights, grid, stream, noise)
+def case(shape, dtype, m, kset, weights=None, grid="shared", stream=False, noise=NOISE, uniform=True):
+    return Case(shape, dtype, m, kset, weights, grid, stream, noise, uniform)
 
 
 def case_id(c):
-    return "%s-m%d-%s%s%s%s" % (c.shape, c.m, "f64" if c.dtype == F64 else "f32", {None: "", "shared": "-w", "per": "-wB"}[c.weights],
-                                "-tB" if c.grid == "per" else "", "-stream" if c.stream else "") + "@" + set_name(c.set)
+    return "%s-m%d-%s%s%s%s%s" % (c.shape, c.m, "f64" if c.dtype == F64 else "f32", {None: "", "shared": "-w", "per": "-wB"}[c.weights],
+                                  "-tB" if c.grid == "per" else "", "-stream" if c.stream else "",
+                                  "" if c.uniform else "-nu") + ("" if c.noise == NOISE else "-noise%g" % c.noise) + "@" + set_name(c.set)
+
+
+def _seed(c):
+    """the seed of a case's data: the record without the `uniform` field where that is the default, so that the cases older
+    than the field keep their data bit for bit"""
+    return zlib.crc32(repr(tuple(c)[:8] if c.uniform else tuple(c)).encode())
 
 
 def _rt_cases(shape, n, q, p, sizes, blk_m):
@@ -229,9 +241,11 @@ def case_data(c):
     """the handle's inputs, in the handle's dtype: x (m,) or (B, m), Y (B, m), w None / (m,) / (B, m), alpha (B, q) = the
     truth times 1.00 .. 1.04 per problem; every problem has its own coefficients and noise (seed: the case)"""
     s, T = SHAPES[c.shape], NP_DTYPE[c.dtype]
-    rng = np.random.default_rng(zlib.crc32(repr(tuple(c)).encode()))
+    rng = np.random.default_rng(_seed(c))
     n, q = len(s.kinds), len(s.truth)
     x = np.linspace(0.0, s.span, c.m)
+    if not c.uniform and c.grid != "per":  # every interior point moved by up to 0.4 of the spacing: still increasing
+        x[1:-1] += 0.8 * (rng.random(c.m - 2) - 0.5) * s.span / (c.m - 1)
     if c.grid == "per":  # every problem its own span, every grid non-uniform
         x = np.stack([np.sort(rng.random(c.m)) * s.span * (1.0 + 0.05 * b) for b in range(B)])
     x = np.ascontiguousarray(x, dtype=T)
@@ -373,7 +387,7 @@ FIT_CASES = [
 @functools.lru_cache(maxsize=None)
 def fit_guess(c):
     d = case_data(c)
-    rng = np.random.default_rng(zlib.crc32(repr(tuple(c)).encode()) + 1)
+    rng = np.random.default_rng(_seed(c) + 1)
     g = np.asarray(SHAPES[c.shape].truth) * rng.uniform(0.95, 1.05, d["alpha"].shape)
     g = np.ascontiguousarray(g, dtype=d["alpha"].dtype)
     g.setflags(write=False)

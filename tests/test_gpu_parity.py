@@ -24,20 +24,34 @@ def _rel(a, b, scale):
     return np.abs(a - b).max() / scale
 
 
-def _check_eval(mdl, x, Y, alpha, w=None, tol=TOL):
-    bp = vp.BatchProblem(mdl, Y, x=x, weights=w)
+def _oracle_evaluate(mdl, x, Y, alpha, w):
+    """O.evaluate_batch; per-problem grids (B, m) and weights (B, m) problem by problem"""
+    if np.ndim(x) == 1 and (w is None or np.ndim(w) == 1):
+        return O.evaluate_batch(mdl, x, Y, alpha, w=w, n_threads=4)
+    parts = [O.evaluate_batch(mdl, x if np.ndim(x) == 1 else x[b], Y[b:b + 1], alpha[b:b + 1],
+                              w=w if w is None or np.ndim(w) == 1 else w[b]) for b in range(Y.shape[0])]
+    return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
+
+def _check_eval(mdl, x, Y, alpha, w=None, tol=TOL, bp=None):
+    """bp: an open handle on these inputs (it stays open), else one is made of them; x and w may be per problem, (B, m)"""
+    own = bp is None
+    if own:
+        bp = vp.BatchProblem(mdl, Y, x=x, weights=w)
     got = bp.evaluate(alpha)
-    ref = O.evaluate_batch(mdl, x, Y, alpha, w=w, n_threads=4)
+    ref = _oracle_evaluate(mdl, x, Y, alpha, w)
     assert (got["status"] == 0).all() and (ref["status"] == 0).all()
     B = Y.shape[0]
     yw = Y if w is None else Y * w
     for b in range(B):
+        xb = x if np.ndim(x) == 1 else x[b]
+        wb = 1.0 if w is None else (w if np.ndim(w) == 1 else w[b])
         assert _rel(got["C"][b], ref["C"][b], np.abs(ref["C"][b]).max()) <= tol, "C of problem %d" % b
         assert _rel(got["r"][b], ref["r"][b], np.abs(yw[b]).max()) <= tol, "r of problem %d" % b
         for k in range(mdl.n_params):
             # |dJ_k| <= tol*max|J_k| + rounding floor relative to the un-projected column W D_k c
             # (J_k = -P_perp (W D_k c) cancels; for m == n it is identically zero)
-            dkc = (O.eval_dphi(mdl, x, alpha[b], k) * ref["C"][b][:, None]).sum(0) * (1.0 if w is None else w)
+            dkc = (O.eval_dphi(mdl, xb, alpha[b], k) * ref["C"][b][:, None]).sum(0) * wb
             bound = tol * np.abs(ref["J"][b, k]).max() + 1e-13 * np.abs(dkc).max()
             assert np.abs(got["J"][b, k] - ref["J"][b, k]).max() <= bound, "J[%d] of problem %d" % (k, b)
         # cost is an absolute quantity of size ||y_w||^2 * eps at a perfect fit
@@ -51,7 +65,9 @@ def _check_eval(mdl, x, Y, alpha, w=None, tol=TOL):
     assert np.array_equal(np.asarray(bp.jacobian()), got["J"])
     assert np.abs(np.asarray(bp.linear_coefficients()) - got["C"]).max() <= 1e-11 * np.abs(got["C"]).max()
     assert np.abs(np.asarray(bp.cost()) - got["cost"]).max() <= 1e-11 * max(got["cost"].max(), ymax ** 2 * 1e-6)
-    bp.close()
+    if own:
+        bp.close()
+    return got
 
 
 @pytest.mark.parametrize("m", [3, 11, 64, 100, 128, 129, 200, 256, 257, 500, 512, 513, 1000, 1023, 1024])

@@ -61,7 +61,7 @@ ABI_SYMBOLS = [
 
 # test hooks (include/varpro_hip_debug.h): exported by the library, not part of the drop-in boundary
 DEBUG_SYMBOLS = ["vp_debug_gram_evaluate", "vp_debug_lmpar_gram", "vp_debug_set_refit", "vp_debug_set_column_fit",
-                 "vp_debug_search_ms", "vp_debug_kernel_set", "vp_debug_registry_entry"]
+                 "vp_debug_search_ms", "vp_debug_kernel_set", "vp_debug_registry_entry", "vp_debug_last_fit"]
 
 
 class VarproHipUnavailable(ImportError):
@@ -164,6 +164,8 @@ def load():
     if hasattr(lib, "vp_debug_kernel_set"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no such hooks)
         lib.vp_debug_kernel_set.argtypes = [vp, i32p]
         lib.vp_debug_registry_entry.argtypes = [C.c_int, i32p]
+    if hasattr(lib, "vp_debug_last_fit"):
+        lib.vp_debug_last_fit.argtypes = [vp, i32p]
     lib.vp_statistics.argtypes = [vp, vp, vp, vp, vp]
     lib.vp_global_statistics.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.vp_summary.argtypes = [vp, dp]

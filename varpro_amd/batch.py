@@ -610,6 +610,14 @@ class BatchProblem:
         check(self.lib.vp_debug_kernel_set(self._h, rec))
         return tuple(int(v) for v in rec)
 
+    def last_fit_kernel(self):
+        """test hook (vp_debug_last_fit): (kernel, padding, weighted, 0) of the launch the last fit issued -- kernel 0 = no fit
+        yet, 1 = wave, 2 = slots, 3 = Gram (fp32 handle, fp64 Gram matrix), 4 = row-block, 5 = generic; padding 1 = m fills the set, 2 = last register pair,
+        0 = general, -1 = not applicable"""
+        rec = (C.c_int32 * 4)()
+        check(self.lib.vp_debug_last_fit(self._h, rec))
+        return tuple(int(v) for v in rec)
+
     @_device_entry
     def best_fit(self):
         """== FitResult::best_fit (src/fit.rs:55-59, 87-91)"""

@@ -378,6 +378,7 @@ struct __attribute__((visibility("hidden"))) vp_batch {
     int32_t *d_rescue = nullptr; // [2 + B]: two ping-pong counters + the flagged problems of the running fit
     void *d_rescue_ws = nullptr; // kRescueBlocks workspace slots of the generic fit kernel
     int rescue_slot = 0;         // the counter the NEXT fit appends to
+    int32_t last_fit[4] = {0, 0, 0, 0}; // vp_debug_last_fit: the record of the launcher that issued the last fit's launch
     bool rescue_off = false;     // vp_debug_set_refit(h, 0): fits keep the kernels' own `Numerical`
 };
 
@@ -2026,6 +2027,7 @@ int rescue_refit(vp_batch *h, const LaunchParams &fit_params) {
     // than that, weights, per-problem grids, models without that kernel -- on the generic kernel, which also zeroes the
     // list's other counter
     p.gen_list_first = 0;
+    p.last_fit = nullptr; // (the record names the fit's own launch, not the re-fit of what it flagged)
     if (launch_fn fast = find_fit_rescue(h->kern->fit_single)) {
         const int rc = fast(p);
         if (rc == VP_ERR_OK) p.gen_list_first = kFitRescueGrid;
@@ -2087,6 +2089,7 @@ int vp_fit_trace(vp_batch *h, const vp_lm_opts *opts, void *alpha_inout, void *C
     if (int rc0 = rescue_prepare(h, p)) return rc0;
     int list_used = 0; // (set by the launcher when its kernel may append to the list)
     p.rescue_used = &list_used;
+    p.last_fit = h->last_fit;
     Timer tm(h, VP_KERNEL_FIT);
     int rc = fit_fn(p);
     if (rc == VP_ERR_OK && list_used) rc = rescue_refit(h, p); // (the problems the fit kernel flagged and did not re-fit itself)
@@ -2335,6 +2338,13 @@ int vp_debug_kernel_set(vp_batch *h, int32_t out[8]) {
     if (!h || !h->kern) return fail(VP_ERR_INVALID, "null handle");
     if (!out) return fail(VP_ERR_INVALID, "null out");
     kernel_set_record(*h->kern, out);
+    return VP_ERR_OK;
+}
+
+int vp_debug_last_fit(vp_batch *h, int32_t out[4]) {
+    if (!h) return fail(VP_ERR_INVALID, "null handle");
+    if (!out) return fail(VP_ERR_INVALID, "null out");
+    for (int i = 0; i < 4; ++i) out[i] = h->last_fit[i];
     return VP_ERR_OK;
 }
 

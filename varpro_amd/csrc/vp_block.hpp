@@ -958,6 +958,7 @@ template <typename T, class M> int launch_fit(const LaunchParams &p) {
     // heavy-tailed: mean ~8, max 100+): four waves per problem then shorten every chain ~3.5x at no cost in throughput that
     // matters there.  Results do not depend on the choice beyond rounding (a different but equally valid TSQR tree).
     constexpr int WM = 4;
+    record_fit(p, kFitKernelBlock, -1, p.w != nullptr);
     const bool multi = p.B <= (int64_t)16 * (p.num_cus > 0 ? p.num_cus : 256) && p.m >= VP_BLK_MULTI_MIN_BLOCKS * WM * 64 * RB && WM * (M::N + 1 + M::P) <= 128;
     // (long problems: taller blocks, one wave per SIMD -- block_rows_long)
     constexpr int RLU = block_rows_long<T, M, false>(), RLW = block_rows_long<T, M, true>(), RLT = block_rows_long<T, M, false, true>();

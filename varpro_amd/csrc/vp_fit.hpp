@@ -1551,12 +1551,19 @@ template <typename T, class M, int R, int W = 1> int launch_fit(const LaunchPara
     if (a.B <= 0) return VP_ERR_OK;
     if (p.rescue_used) *p.rescue_used = 1;
     const size_t lds = fit_lds_bytes<T, M, R, W>(p.w != nullptr);
-    if (p.w) hipLaunchKernelGGL((fit_kernel<T, M, R, W, true>), dim3((unsigned)a.B), dim3(64 * W), lds, p.stream, a);
-    else if (p.m == 64 * R * W)
+    if (p.w) {
+        record_fit(p, kFitKernelWave, 0, true);
+        hipLaunchKernelGGL((fit_kernel<T, M, R, W, true>), dim3((unsigned)a.B), dim3(64 * W), lds, p.stream, a);
+    } else if (p.m == 64 * R * W) {
+        record_fit(p, kFitKernelWave, 1, false);
         hipLaunchKernelGGL((fit_kernel<T, M, R, W, false, 1>), dim3((unsigned)a.B), dim3(64 * W), lds, p.stream, a);
-    else if (R > 2 && p.m > 64 * (R - 2) * W)
+    } else if (R > 2 && p.m > 64 * (R - 2) * W) {
+        record_fit(p, kFitKernelWave, 2, false);
         hipLaunchKernelGGL((fit_kernel<T, M, R, W, false, 2>), dim3((unsigned)a.B), dim3(64 * W), lds, p.stream, a);
-    else hipLaunchKernelGGL((fit_kernel<T, M, R, W, false>), dim3((unsigned)a.B), dim3(64 * W), lds, p.stream, a);
+    } else {
+        record_fit(p, kFitKernelWave, 0, false);
+        hipLaunchKernelGGL((fit_kernel<T, M, R, W, false>), dim3((unsigned)a.B), dim3(64 * W), lds, p.stream, a);
+    }
     return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
 }
 

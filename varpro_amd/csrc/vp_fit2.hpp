@@ -1268,13 +1268,24 @@ template <typename T, class M, int R, int W = 1> int launch_fit2(const LaunchPar
         if (hipMemsetD32Async((hipDeviceptr_t)p.queue, (int)(blocks * NG * GS), 1, p.stream) != hipSuccess) return VP_ERR_HIP;
         const size_t lds = (size_t)64 * R * W * sizeof(T) * (1 + (size_t)NG * GS) + (size_t)NG * GS * sizeof(SlotRec<T, M::N, M::Q>) +
                            sizeof(SlotConsts<T>) + (size_t)((GS + 3) / 4) * 4 * sizeof(int) + (size_t)group_xch_bytes<W>() + 16;
-        if (lds > (size_t)(160 * 1024) / BPC) return launch_fit<T, M, R, W>(p); // (never with the slot count above; a guard)
+        // fit2_slots rounds a budget of less than one slot up to one; the workgroup then needs more than its share of the CU's
+        // LDS.  ONE registered set is in that case and always takes this exit: the single exponential + offset at 32 fp64 rows
+        // per lane (16 KiB per column, two workgroups per CU: 5 columns + records > 80 KiB) -- its three slot kernels are built
+        // and never launched (tests/fit_cases.py: NO_ROOM_FOR_SLOTS; vp_debug_last_fit reports the wave kernel)
+        if (lds > (size_t)(160 * 1024) / BPC) return launch_fit<T, M, R, W>(p);
 #define VP_F2(PADM_)                                                                                                   \
     hipLaunchKernelGGL((fit2_kernel<T, M, R, W, PADM_, GS, NG, WPS>), dim3((unsigned)blocks), dim3(64 * W * NG), lds,   \
                        p.stream, args)
-        if (p.m == 64 * R * W) VP_F2(1);
-        else if (R > 2 && p.m > 64 * (R - 2) * W) VP_F2(2);
-        else VP_F2(0);
+        if (p.m == 64 * R * W) {
+            record_fit(p, kFitKernelSlots, 1, false);
+            VP_F2(1);
+        } else if (R > 2 && p.m > 64 * (R - 2) * W) {
+            record_fit(p, kFitKernelSlots, 2, false);
+            VP_F2(2);
+        } else {
+            record_fit(p, kFitKernelSlots, 0, false);
+            VP_F2(0);
+        }
 #undef VP_F2
         return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
     }

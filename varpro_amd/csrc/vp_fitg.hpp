@@ -1166,6 +1166,7 @@ template <class M> int launch_fitg(const LaunchParams &p, double *dbg = nullptr)
     if (blocks > cap_groups) blocks = cap_groups;
     if (hipMemsetD32Async((hipDeviceptr_t)p.queue, (int)(blocks * ns_used), 1, p.stream) != hipSuccess) return VP_ERR_HIP;
     const dim3 grid((unsigned)blocks), block(64 * VP_FITG2_WAVES);
+    record_fit(p, kFitKernelGram, -1, weighted);
     if (uniform && !weighted) hipLaunchKernelGGL((fitg2_kernel<M, NS, true, false>), grid, block, 0, p.stream, a);
     else if (uniform) hipLaunchKernelGGL((fitg2_kernel<M, NS, true, true>), grid, block, 0, p.stream, a);
     else if (!weighted) hipLaunchKernelGGL((fitg2_kernel<M, NS, false, false>), grid, block, 0, p.stream, a);

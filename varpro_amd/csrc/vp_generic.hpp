@@ -1253,6 +1253,7 @@ template <typename T> int launch_fit(const LaunchParams &p) {
     if (a.B <= 0) return VP_ERR_OK;
     a.scale_cols = 1; // (this kernel never flags a problem for a re-fit: it IS the re-fit)
     const size_t lds = gen_lds_for<T>(a, &gen_fit_kernel<T>);
+    record_fit(p, kFitKernelGeneric, -1, p.w != nullptr);
     hipLaunchKernelGGL((gen_fit_kernel<T>), dim3((unsigned)p.gen_blocks), dim3(TB), lds, p.stream, a);
     return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
 }

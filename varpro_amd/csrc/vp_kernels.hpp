@@ -94,12 +94,24 @@ struct LaunchParams {
     int rescue_slot;         // the counter this fit appends to (0 / 1); the re-fit launch zeroes the other one
     int *rescue_used;        // (host) set to 1 by a launcher whose kernel may append to the list (the slot kernels of models
                              // with the scaled re-fit built in re-fit what they flag themselves: nothing to launch afterwards)
+    int32_t *last_fit;       // (host) [4], vp_debug_last_fit: written by the launcher that issues the fit launch -- {kernel,
+                             // padding variant, weighted instantiation, 0}; null: nobody asked
     const int32_t *gen_list; // generic fit kernel: fit the problems gen_list[2 + i], i < gen_list[gen_list_slot] (null: all B)
     int gen_list_slot;
     int gen_list_first;      // ... starting at entry gen_list_first (the ones before it were re-fitted by the set's own kernel)
     int gen_scale_cols;      // generic kernels: power-of-two scaling of huge basis columns (and their derivative columns)
     hipStream_t stream;
 };
+
+// vp_debug_last_fit's record: which fit kernel a launcher issued (include/varpro_hip_debug.h)
+enum { kFitKernelWave = 1, kFitKernelSlots = 2, kFitKernelGram = 3, kFitKernelBlock = 4, kFitKernelGeneric = 5 };
+inline void record_fit(const LaunchParams &p, int kernel, int padding, bool weighted) {
+    if (!p.last_fit) return;
+    p.last_fit[0] = kernel;
+    p.last_fit[1] = padding;
+    p.last_fit[2] = weighted ? 1 : 0;
+    p.last_fit[3] = 0;
+}
 
 // workgroups of the fast re-fit launch (fit_kernel<..., RESCUE>, vp_fit.hpp): flagged problems beyond that go to the generic kernel
 constexpr int kFitRescueGrid = 256;
