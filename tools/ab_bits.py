@@ -193,6 +193,8 @@ for rnd in range(rounds):
             if ln.startswith("B=") or ln.startswith("LEG "):
                 print("%-28s %s" % (os.path.basename(lib), ln), flush=True)
                 w = ln.split()
+                if w[0].startswith("B="):  # (plain mode) "B=65536 m=1024: evals N  sha H"
+                    record.append({"library": os.path.basename(lib), "round": rnd, "B": int(w[0][2:]), "m": int(w[1][2:-1]), "evaluations": int(w[3]), "sha256_16": w[5]})
                 if w[0] == "LEG": record.append(dict({"library": os.path.basename(lib), "round": rnd, "leg": w[1]},
                                    **{w[i]: (w[i + 1] if w[i] == "sha" else float(w[i + 1])) for i in range(2, len(w) - 1, 2)}))
         if o.returncode != 0:

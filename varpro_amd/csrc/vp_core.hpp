@@ -65,8 +65,10 @@ __device__ __forceinline__ void house_qr(T (&C)[NC][R], T (&g)[N], T (&Rm)[N][N]
             d[j - k] = acc;
             top[j - k] = C[j][L::reg_of_row(prow)]; // pivot-row entry a_j[prow] (valid in the owning lane)
         }
+        chain_raise(grp); // (issue priority of the dependent chain: vp_device.hpp; nothing for a plain Grp)
         group_allreduce(grp, d);
         group_bcast<NREM>(grp, top, L::lane_of_row(prow));
+        chain_reduced(grp);
         // beta = -sign(alpha) sigma, sigma = ||a_k||;  u = alpha - beta = sign(alpha)(|alpha| + sigma);
         // g = 1/(beta u) = -1/(sigma (|alpha| + sigma)) = -rsqrt(d_k) / (|alpha| + sigma): one rsq, one rcp, no
         // division / sqrt expansion on the critical path.  A zero column (d_k == 0) leaves H = I; a non-finite
@@ -81,6 +83,7 @@ __device__ __forceinline__ void house_qr(T (&C)[NC][R], T (&g)[N], T (&Rm)[N][N]
         const T gk = live ? -y * frcp(tabs(alpha) + sigma) : T(0);
         g[k] = gk;
         Rm[k][k] = beta;
+        chain_drop(grp);
         // v_k in place: row prow := u (rows above are already 0)
 #pragma unroll
         for (int r = 0; r < L::VW && r < R; ++r) {
@@ -523,8 +526,10 @@ __device__ __forceinline__ void evaluate_core_const_first(const M &mdl, const T 
     }
 #pragma unroll
     for (int j = 0; j < NCX; ++j) top[j] = C[j][L::reg_of_row(0)];
+    chain_raise(grp);
     group_allreduce(grp, d);
     group_bcast<NCX>(grp, top, L::lane_of_row(0));
+    chain_reduced(grp);
     T Rm[N][N], qty[N];
     T tau[NCX];
     // (opaque: 1 / beta_0 and its square in solve_coeffs are loop invariants of the caller's LM loop -- hoisted, they are two
@@ -545,6 +550,7 @@ __device__ __forceinline__ void evaluate_core_const_first(const M &mdl, const T 
         if (j < NE) Rm[0][1 + j] = tj;
         if (j == NE) qty[0] = tj;
     }
+    chain_drop(grp);
 #pragma unroll
     for (int r0 = 0; r0 < R; r0 += VW) {
         T tt[2], sc[2];
@@ -572,6 +578,7 @@ __device__ __forceinline__ void evaluate_core_const_first(const M &mdl, const T 
     }
     T cp[N];
     bool truncated;
+    chain_raise_scalar(grp); // (the triangular solve: one wave-uniform chain)
     solve_coeffs<T, N>(Rm, qty, eps, cp, u.e, truncated);
 #pragma unroll
     for (int j = 0; j < NE; ++j) u.c[j] = cp[1 + j];
@@ -579,6 +586,7 @@ __device__ __forceinline__ void evaluate_core_const_first(const M &mdl, const T 
     u.g[0] = h0.g;
 #pragma unroll
     for (int j = 0; j < NE; ++j) u.g[1 + j] = g1[j];
+    chain_drop(grp);
     // ||r||^2 = ||e||^2 + sum_{rows >= N} (Q^T y)^2
     T s = T(0);
 #pragma unroll
@@ -586,7 +594,9 @@ __device__ __forceinline__ void evaluate_core_const_first(const M &mdl, const T 
         const T v = (r >= VW || L::row_of(r, lane) >= N) ? C[NE][r] : T(0);
         s = tfma(v, v, s);
     }
+    chain_raise(grp);
     T fn2 = group_sum(grp, s);
+    chain_reduced(grp);
 #pragma unroll
     for (int k = 0; k < N; ++k) fn2 = tfma(u.e[k], u.e[k], fn2);
     u.fn2 = fn2;
@@ -596,6 +606,7 @@ __device__ __forceinline__ void evaluate_core_const_first(const M &mdl, const T 
 #pragma unroll
     for (int k = 0; k < N; ++k) ok = ok && is_finite(u.c[k]) && is_finite(Rm[k][k]);
     u.ok = uni(ok);
+    chain_drop(grp);
 }
 
 // Projected residual in Q-coordinates: rows < N <- e, rows >= N keep Q^T y.  (in place on the data column)

@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 // LDS-typed pointers (address space 3): accesses through them stay ds_* instructions in out-of-line functions
 #define VP_LDS __attribute__((address_space(3)))
@@ -119,6 +120,46 @@ template <int W_> struct Grp {
         return g;
     }
 };
+
+// ---- issue priority of dependent chains (the slot kernel's VP_FIT2_CHAIN_PRIO, vp_fit2.hpp) ----------------------
+// A Householder step ends in a packed wave reduction and a wave-uniform fp64 chain (sqrt, reciprocal, Newton steps): ~25 + ~20
+// DEPENDENT instructions, during which the wave waits on every link while the partner wave of the SIMD streams FMAs through
+// the same issue port.  s_setprio only changes which READY wave issues first; a kernel opts in through its group type
+// (ChainGrp instead of Grp), so the shared routines (house_qr, evaluate_core_const_first, jac_qrfac_scaled) compile to the
+// same code as before for every other kernel: the helpers below are empty for a plain Grp.
+//   MODE 1: raised from the start of a reduction to the next row loop, and for wave-uniform scalar sections
+//   MODE 2: raised for the reductions / broadcasts only
+//   MODE 3: as 1, and the slot kernel's lane-parallel scalar phase (two active lanes, one long chain) one level higher still
+template <int W_, int MODE_> struct ChainGrp : Grp<W_> {
+    static constexpr int kChainPrio = MODE_;
+    __device__ __forceinline__ static ChainGrp make(unsigned char *xch_) {
+        ChainGrp g;
+        static_cast<Grp<W_> &>(g) = Grp<W_>::make(xch_);
+        return g;
+    }
+};
+template <class G, class = void> struct chain_prio_mode : std::integral_constant<int, 0> {};
+template <class G> struct chain_prio_mode<G, std::void_t<decltype(G::kChainPrio)>> : std::integral_constant<int, G::kChainPrio> {};
+// before a reduction / broadcast
+template <class G> __device__ __forceinline__ void chain_raise(const G &) {
+    if constexpr (chain_prio_mode<G>::value != 0) __builtin_amdgcn_s_setprio(1);
+}
+// between the reduction and the wave-uniform scalar code that follows it
+template <class G> __device__ __forceinline__ void chain_reduced(const G &) {
+    if constexpr (chain_prio_mode<G>::value == 2) __builtin_amdgcn_s_setprio(0);
+}
+// before a wave-uniform scalar section that no reduction opens
+template <class G> __device__ __forceinline__ void chain_raise_scalar(const G &) {
+    if constexpr (chain_prio_mode<G>::value == 1 || chain_prio_mode<G>::value == 3) __builtin_amdgcn_s_setprio(1);
+}
+// before the slot kernel's scalar phase
+template <class G> __device__ __forceinline__ void chain_raise_phase(const G &) {
+    if constexpr (chain_prio_mode<G>::value == 3) __builtin_amdgcn_s_setprio(3);
+}
+// before the next row loop (column build, dot products, reflector updates)
+template <class G> __device__ __forceinline__ void chain_drop(const G &) {
+    if constexpr (chain_prio_mode<G>::value == 1 || chain_prio_mode<G>::value == 3) __builtin_amdgcn_s_setprio(0);
+}
 
 // ---- cross-lane data movement -----------------------------------------------------------------
 // DPP move: lanes of rows enabled in ROW_MASK receive the permuted value, all other lanes receive 0

@@ -687,6 +687,25 @@ __device__ __forceinline__ void jac_qrfac(T (&Z)[Q][R], T (&rv)[R], T (&Rj)[Q][Q
 #ifndef VP_JAC_Q2_NOSWAP
 #define VP_JAC_Q2_NOSWAP 1
 #endif
+// Each order has a "zero pivot column" exit in step 0 that leaves the other column and the residual column as they are, next to
+// the ordinary path that updates both.  With even odds on that branch the register allocator (the sweep holds all 256 VGPRs)
+// splits the two columns' live ranges BEFORE it: one side of the pivot compare copied both columns, 16 rows each, into the
+// registers of the updated ones -- 32 v_mov_b64 in front of step 0, taken by half of all accepted steps; the exchange that
+// VP_JAC_Q2_NOSWAP took out of the source, back as copies.  (They are not phi copies of the point where the two orders meet:
+// a statement that keeps step 1 inside each order moved step 1 and not one copy.)  On: the exit is marked as the rare branch it
+// is, and the copies move into it (tools/isa_block_movs.py, profiles/chain_prio_isa.json).  The same statements on the same
+// operands in the same order: bit-identical.  OFF: alone 2.0270-2.0298 ms per step against the parent's 2.0295-2.0328 (five
+// alternating rounds, two batches in flight, profiles/chain_prio_ab_inflight.json) -- its slowest round does not beat the
+// parent's fastest --, and with VP_FIT2_CHAIN_PRIO 2.0049-2.0107 against 2.0032-2.0083 without it: the partner wave covers the
+// copies, instruction count is not time ("Issue slots of the bulk")
+#ifndef VP_JAC_Q2_NOCOPY
+#define VP_JAC_Q2_NOCOPY 0
+#endif
+#if VP_JAC_Q2_NOCOPY
+#define VP_Q2_RARE(c) __builtin_expect((c), 0)
+#else
+#define VP_Q2_RARE(c) (c)
+#endif
 template <typename T, int R, int ROW0, bool SWAP, class G>
 __device__ __forceinline__ void jac_q2_ordered(T (&Z)[2][R], T (&rv)[R], const T (&s_in)[2], const T (&Gm)[2][2], const T (&bz)[2],
                                                T (&Rj)[2][2], int (&ipvt)[2], T (&qtf)[2], G &grp) {
@@ -701,18 +720,21 @@ __device__ __forceinline__ void jac_q2_ordered(T (&Z)[2][R], T (&rv)[R], const T
     { // ---- step 0: raw dots from the Gram round
         constexpr int prow = ROW0;
         T top[3] = {Z[PC][L::reg_of_row(prow)], Z[OC][L::reg_of_row(prow)], rv[L::reg_of_row(prow)]};
-        group_bcast<3>(grp, top, L::lane_of_row(prow));
+        group_bcast<3>(grp, top, L::lane_of_row(prow)); // (the caller's Gram round raised the issue priority: chain_raise)
+        chain_reduced(grp);
         const T dz0 = Gm[PC][PC], dz1 = Gm[PC][OC], dr = bz[PC];
         T an = usqrt(dz0);
-        if (uni(tabs(sc0) * an == T(0) || dz0 <= num<T>::norm2_min)) {
+        if (VP_Q2_RARE(uni(tabs(sc0) * an == T(0) || dz0 <= num<T>::norm2_min))) {
             rdiag0 = T(0);
             Rj[0][1] = sc1 * top[1];
             qtf[0] = top[2];
+            chain_drop(grp);
         } else {
             const T piv = top[0];
             if (piv < T(0)) an = -an;
             const T vp = piv + an;
             const T gj = -frcp(an * vp);
+            chain_drop(grp);
 #pragma unroll
             for (int r = 0; r < L::VW && r < R; ++r) {
                 const int i = L::row_of(r, lane);
@@ -750,11 +772,13 @@ __device__ __forceinline__ void jac_q2_ordered(T (&Z)[2][R], T (&rv)[R], const T
             w[0] = a0;
             w[1] = a1;
         }
+        chain_raise(grp);
         group_allreduce(grp, w);
         T top[2] = {Z[OC][L::reg_of_row(prow)], rv[L::reg_of_row(prow)]};
         group_bcast<2>(grp, top, L::lane_of_row(prow));
+        chain_reduced(grp);
         T an = usqrt(w[0]);
-        if (uni(tabs(sc1) * an == T(0) || w[0] <= num<T>::norm2_min)) {
+        if (VP_Q2_RARE(uni(tabs(sc1) * an == T(0) || w[0] <= num<T>::norm2_min))) {
             rdiag1 = T(0);
             qtf[1] = top[1];
         } else {
@@ -770,6 +794,7 @@ __device__ __forceinline__ void jac_q2_ordered(T (&Z)[2][R], T (&rv)[R], const T
     }
     Rj[0][0] = sc0 * rdiag0;
     Rj[1][1] = sc1 * rdiag1;
+    chain_drop(grp);
 }
 
 // The same factorisation for a Jacobian given as COLUMN-SCALED columns  z_k = s_k g_k  (Kaufman: z_k = -c_k Q^T D_k for
@@ -809,6 +834,7 @@ __device__ __forceinline__ void jac_qrfac_scaled(T (&Z)[Q][R], T (&rv)[R], const
             for (int r = 0; r < R; ++r) acc = tfma(Z[a][r], rv[r], acc);
             gr[idx++] = acc;
         }
+        if constexpr (Q == 2 && VP_JAC_Q2_NOSWAP) chain_raise(grp); // (held through jac_q2_ordered's broadcast; only that path has the helpers)
         group_allreduce(grp, gr);
         idx = 0;
 #pragma unroll

@@ -72,6 +72,22 @@ template <typename T, int N, int Q> struct alignas(8) SlotRec {
 #ifndef VP_FIT2_SKIP_REFILL
 #define VP_FIT2_SKIP_REFILL 0 /* the scalar phase reports whether any slot of the group terminated; when none did the refill loop and its trailing group_sync are skipped in one branch (a slot finishes once in ~9 evaluations).  OFF: +0.5 % alone, nothing on top of SCALARS -- the refill section's 600 cycles are covered by the partner wave */
 #endif
+// Issue slots of the bulk ("Issue slots of the bulk"): with two waves per SIMD a wave in one of its dependent
+// chains -- the packed reduction that ends every Householder step, the wave-uniform fp64 code behind it, the triangular solve, the
+// scalar phase -- competes for the issue port with its partner's ready FMA stream.  The wave raises its issue priority (s_setprio)
+// for those sections and drops it for the row loops (column build, dot products, reflector updates).  The priority only picks among
+// READY waves: bit-identical.  The call sites sit in the shared routines behind the group type (ChainGrp, vp_device.hpp): no other
+// kernel's code changes.  The lone tail follows the switch.  Each value measured alone against the parent's sources, five alternating
+// rounds, two batches in flight (profiles/chain_prio_ab_inflight.json; parent 2.0295-2.0328 ms, and 2.0287-2.0343 in the second set):
+//   1 (on)  from the start of a reduction to the next row loop, around the triangular solve, and from the end of a slot's sweep
+//           through the scalar phase: 2.0032-2.0083 ms (second set 2.0013-2.0066), -1.3 %, slowest round 0.021 ms under the parent's
+//           fastest at a parent spread of 0.003
+//   2       the reductions and broadcasts only: 2.0278-2.0297, inside the parent's spread -- the gain of 1 is the scalar code
+//   3       as 1 with the scalar phase one level higher still: 2.0040-2.0128, no better than 1
+#ifndef VP_FIT2_CHAIN_PRIO
+#define VP_FIT2_CHAIN_PRIO 1
+#endif
+template <int W> using SlotGrp = std::conditional_t<VP_FIT2_CHAIN_PRIO != 0, ChainGrp<W, VP_FIT2_CHAIN_PRIO>, Grp<W>>;
 #if VP_FIT2_LOCAL_CALLS
 #define VP_SLOT_FN static __noinline__
 #else
@@ -564,7 +580,7 @@ __device__ VP_LONE_TAIL_LINKAGE void fit2_lone_tail(VP_LDS SlotRec<T, M::N, M::Q
                                             const T h0_beta, const T h0_u, const T h0_g) {
     constexpr int N = M::N, P = M::P, Q = M::Q;
     constexpr int NC = N + P, YC = N - 1, DC = YC + 1;
-    using G = Grp<1>;
+    using G = SlotGrp<1>;
     G grp = G::make(nullptr);
     const int lane = grp.gl;
     using Src = RowSource<T, R, true, 0, 1, 1, true, PADM>;
@@ -675,6 +691,7 @@ __device__ VP_LONE_TAIL_LINKAGE void fit2_lone_tail(VP_LDS SlotRec<T, M::N, M::Q
         load_rows_lds<T, R, 1>((const T *)s_col, lane, C[YC]);
         evaluate_core_const_first<T, M, R, NC, Src, G, true>(mdl, xt, src, eps, grp, h0, C, u, nullptr, qty0);
         asm volatile("" ::: "memory");
+        chain_raise_scalar(grp); // (the inline, wave-uniform bookkeeping: one dependent chain up to the next sweep)
         unpark();
         const T fnorm1 = usqrt(u.fn2);
         bool need_jac = false;
@@ -767,11 +784,13 @@ __device__ VP_LONE_TAIL_LINKAGE void fit2_lone_tail(VP_LDS SlotRec<T, M::N, M::Q
             need_jac = good;
         }
         if (need_jac) {
+            chain_drop(grp);
             residual_qcoords<T, R, N>(C[YC], u.e, grp);
             T zs[Q];
 #pragma unroll
             for (int k = 0; k < Q; ++k) zs[k] = -u.c[k];
             jac_qrfac_scaled<T, R, Q, N>(reinterpret_cast<T(&)[Q][R]>(C[DC]), C[YC], zs, Rj, acnorm, ipvt, qtf, grp);
+            chain_raise_scalar(grp);
             if (uni(jac_not_finite<T, Q>(acnorm))) { // (rare) flag and re-fit: vp_fit.hpp, jac_not_finite
                 term = VP_TERM_NUMERICAL;
                 flagged = true;
@@ -854,7 +873,9 @@ __device__ VP_LONE_TAIL_LINKAGE void fit2_lone_tail(VP_LDS SlotRec<T, M::N, M::Q
         // park for the next sweep
         park();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        chain_drop(grp);
     }
+    chain_drop(grp); // (every `break` above leaves the loop in its raised part)
     // results of the finished problem
     if (lane == 0) {
         vp_report rep;
@@ -920,7 +941,7 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
     SlotConsts<T> *kc = reinterpret_cast<SlotConsts<T> *>(recs_all + (size_t)NG * GS);
     int *s_pop = reinterpret_cast<int *>(kc + 1);                                   // [GS] queue pops (W > 1)
     unsigned char *s_xch = reinterpret_cast<unsigned char *>(s_pop + ((GS + 3) / 4) * 4); // group exchange area (W > 1)
-    using G = Grp<W>;
+    using G = SlotGrp<W>;
     G grp = G::make(s_xch);
     const int lane = grp.gl; // group lane: row ownership
     const int gw = (int)blockIdx.x * NG + gi; // persistent group index
@@ -1039,6 +1060,7 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
             T alpha[Q];
 #pragma unroll
             for (int k = 0; k < Q; ++k) alpha[k] = rec->xt[k];
+            chain_drop(grp); // (raised since the previous slot's sweep, or since the scalar phase)
             const int fl_in = uni(rec->flags);
             const bool first = (fl_in & 1) != 0;
             const T qty0 = rec->qty0;
@@ -1051,6 +1073,7 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
             evaluate_core_const_first<T, M, R, NC, Src, G, true, false, false, kPre>(mdl, alpha, src, eps_, grp, h0, C, u, nullptr, qty0, nullptr,
                                                                                       rec->pre); // (read from LDS where they are used)
 
+            chain_raise_scalar(grp); // (wave-uniform from here to the next slot's sweep, but for the Jacobian's row loops)
             const T fnorm1 = usqrt(u.fn2);
             T actred = T(0), ratio = T(0);
             bool good = false;
@@ -1065,11 +1088,13 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
             int ipvt[Q];
             if (need_jac) {
                 // z_k = -c_k Q^T D_k: factor the unscaled columns in place, the coefficients enter as column scales
+                chain_drop(grp);
                 residual_qcoords<T, R, N>(C[YC], u.e, grp);
                 T zs[Q];
 #pragma unroll
                 for (int k = 0; k < Q; ++k) zs[k] = -u.c[k];
                 jac_qrfac_scaled<T, R, Q, N>(reinterpret_cast<T(&)[Q][R]>(C[DC]), C[YC], zs, Rj, acnorm, ipvt, qtf, grp);
+                chain_raise_scalar(grp);
             }
             if (lane == 0) { // group lane 0
                 rec->fnorm1 = fnorm1;
@@ -1098,6 +1123,7 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
         VP_CK2(0);
 
         // =============================== SCALAR phase: lane s of wave 0 <-> slot s ===============================
+        chain_raise_phase(grp);
 #if VP_FIT2_SKIP_REFILL
         int any_done = 1;
         if (grp.wave == 0) any_done = slot_scalar_phase<T, N, Q, GS>((VP_LDS Rec *)recs, (VP_LDS const SlotConsts<T> *)kc);
@@ -1106,6 +1132,7 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
 #endif
         group_sync();
         VP_CK2(1);
+        chain_drop(grp); // (the refill's column loads are a stream; the scalar phase above ran raised)
 
         // =============================== REFILL finished slots from the queue ===============================
         if constexpr (W > 1) {
