@@ -67,6 +67,9 @@ pub const VP_SEARCH_PER_PROBLEM: i32 = 1;
 /// `vp_poisson_reweight`: variance = max(count, floor) / max(best fit, floor)
 pub const VP_POISSON_NEYMAN: i32 = 0;
 pub const VP_POISSON_MODEL: i32 = 1;
+pub const VP_ROBUST_HUBER: i32 = 0;
+pub const VP_ROBUST_CAUCHY: i32 = 1;
+pub const VP_ROBUST_TUKEY: i32 = 2;
 
 #[link(name = "varpro_hip")]
 extern "C" {
@@ -88,6 +91,13 @@ extern "C" {
     /// (`VP_POISSON_MODEL`: `deviance_out` / `pearson_out` `[B]` f64 or null); S = 1, per-problem weights
     pub fn vp_poisson_reweight(h: *mut vp_batch, y: *const c_void, mode: i32, floor: f64, deviance_out: *mut f64,
         pearson_out: *mut f64) -> i32;
+    /// M-estimator weights `w0 sqrt(omega(u))`, `u = w0 (y - f)/s`, formed on the device from the handle's best fit: `w0` the
+    /// base weights `[B][m]` or null (1), `loss` a `VP_ROBUST_*`, `tuning` 0 = the 95 % efficiency constant, `scale` 0 = the
+    /// normalised median of `|w0 (y - f)|` per problem; `scale_out` / `rho_out` `[B]` f64 or null; S = 1, per-problem weights
+    pub fn vp_robust_reweight(h: *mut vp_batch, y: *const c_void, w0: *const c_void, loss: i32, tuning: f64, scale: f64,
+        scale_out: *mut f64, rho_out: *mut f64) -> i32;
+    /// the handle's current weights, `[m]` or `[B][m]` as created (after `vp_robust_reweight`: the outlier map)
+    pub fn vp_weights(h: *mut vp_batch, w_out: *mut c_void) -> i32;
     /// box bounds of `vp_fit` on a device-column handle: host doubles `[q]` or `[B][q]`, infinite = unbounded, both null clears
     pub fn vp_set_bounds(h: *mut vp_batch, lower: *const f64, upper: *const f64, per_problem: i32) -> i32;
     /// instrument response of a handle whose descriptor has an IRF kind: `[m]` or `[B][m]` in the handle's dtype and address

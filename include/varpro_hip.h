@@ -384,6 +384,50 @@ enum { VP_POISSON_NEYMAN = 0, VP_POISSON_MODEL = 1 };
 int vp_poisson_reweight(vp_batch *h, const void *Y, int mode, double floor,
                         double *deviance_out, double *pearson_out);
 
+/*
+ * Robust fits.  Measured data has outliers (afterpulses, stray-light and cosmic-ray spikes, hot channels); an M-estimator
+ * replaces the square of a residual by a loss rho that grows more slowly.  vp_robust_reweight forms the weights of the
+ * equivalent weighted least-squares problem ON THE DEVICE from the residuals of the handle's current best fit
+ * f = Phi(alpha) c (UNWEIGHTED, as vp_best_fit returns it), replaces the handle's weights and weighted data by them
+ * (vp_robust.hpp), and the next vp_fit uses them:
+ *   e_i = w0_i (y_i - f_i)             w0 [B][m]: the BASE weights, in the handle's dtype and address space; NULL: 1.  They
+ *                                      should make the residuals of the clean data homoscedastic (1/sigma_i; Neyman weights
+ *                                      for counts).  The handle's own weights are overwritten every round, so -- like Y --
+ *                                      the base weights are passed again each time.
+ *   s                                  scale > 0: that value for the whole batch (rounded to the handle's dtype; the choice
+ *                                      when w0 = 1/sigma is known).  scale == 0: per problem the normalised median of the
+ *                                      absolute residuals, s = 1.482602218505602 med, med = 0.5 (a[(me-1)/2] + a[me/2]) of
+ *                                      the sorted |e_i| over the me rows with w0_i != 0 (rows of weight 0 are how a ragged
+ *                                      length is expressed and do not pull the median down), selected exactly.  A problem
+ *                                      with s == 0 (me == 0 included) gets w = w0, Y_w = w0 y, scale 0 and rho 0.
+ *   u_i = e_i / s,  t = |u|/k          k = tuning; 0 selects the 95 %-efficiency constant: 1.345, 2.385, 4.685
+ *   VP_ROBUST_HUBER    omega = 1 for |u| <= k, else k/|u|;      rho = u^2/2, or k|u| - k^2/2 beyond k
+ *   VP_ROBUST_CAUCHY   omega = 1/(1 + t^2);                     rho = (k^2/2) log1p(t^2)
+ *   VP_ROBUST_TUKEY    sqrt(omega) = (1 - t)(1 + t), 0 for t >= 1;   rho = (k^2/6)(1 - (1 - t^2)^3), k^2/6 beyond
+ *   w_i = w0_i sqrt(omega_i),  Y_w,i = w_i y_i
+ *   scale_out [B] f64   s as used;  rho_out [B] f64   sum_i rho(u_i), accumulated in double in a fixed order.  Either may be
+ *                       NULL; both follow the handle's address space.
+ * A fit with these weights held fixed, the weights re-formed from its result and the fit repeated from the previous
+ * parameters has as its fixed point the estimating equations sum_i psi(u_i) w0_i df_i/dtheta = 0, psi = u omega: iterating
+ * {vp_robust_reweight, vp_fit} IS the M-estimate (iterated re-weighting, not a Levenberg-Marquardt on rho).  Cauchy and
+ * Tukey are not convex: start them from a sensible fit.  vp_statistics afterwards is the covariance of the weighted
+ * least-squares problem at the final weights, not a sandwich estimator.
+ * Preconditions and what follows are those of VP_POISSON_MODEL: parameters at which the handle can form its best fit,
+ * a handle created with VP_FLAG_W_PER_PROBLEM and a weights array, S = 1, no padding for m < n, no stepped fit running;
+ * afterwards cached evaluations are invalid, vp_params still returns the parameters, and a device-pointer handle has made
+ * no host visit.  A problem whose status is non-zero keeps its weights and weighted data bit for bit and gets NaN in both
+ * outputs.  A residual that is not finite gives NaN weights (scale == 0: the whole problem, with a NaN scale; scale > 0:
+ * that row), so that the next evaluation latches the problem.
+ * VP_ERR_INVALID: null Y, an unknown loss, a tuning or scale that is negative or not finite, and what VP_POISSON_MODEL
+ * refuses with that code.  VP_ERR_UNSUPPORTED: S > 1, a handle padded for m < n.  A refusal leaves the handle as it was.
+ */
+enum { VP_ROBUST_HUBER = 0, VP_ROBUST_CAUCHY = 1, VP_ROBUST_TUKEY = 2 };
+int vp_robust_reweight(vp_batch *h, const void *Y, const void *w0, int loss, double tuning, double scale,
+                       double *scale_out, double *rho_out);
+/* the handle's current weights, [m] or [B][m] as created, into w_out (a copy on the handle's stream; after
+ * vp_robust_reweight they are the outlier map of the fit).  VP_ERR_INVALID on a handle created without weights. */
+int vp_weights(vp_batch *h, void *w_out);
+
 /* Box bounds on the nonlinear parameters of vp_fit, device-column handles only (see "device-column handles" above).
  * lower / upper: HOST pointers to doubles whatever the handle's dtype and flags, [q] (per_problem = 0) or [B][q];
  * -INFINITY / +INFINITY = unbounded on that side; both NULL clears the bounds.  Stays set across vp_fit calls and

@@ -27,6 +27,7 @@ VP_FLAG_DEVICE_COLUMNS = 64
 VP_BASIS_SKIP_INVARIANT = 1
 VP_SEARCH_PER_PROBLEM = 1
 VP_POISSON_NEYMAN, VP_POISSON_MODEL = 0, 1
+VP_ROBUST_HUBER, VP_ROBUST_CAUCHY, VP_ROBUST_TUKEY = 0, 1, 2
 VP_BASIS_CONST, VP_BASIS_EXP_DECAY, VP_BASIS_EXP_RATE, VP_BASIS_EXP_COS, VP_BASIS_SIN_PHASE, VP_BASIS_EXTERNAL = 0, 1, 2, 3, 4, 5
 VP_BASIS_GAUSS, VP_BASIS_LORENTZ, VP_BASIS_LINEAR = 6, 7, 8
 VP_BASIS_EXP_DECAY_IRF, VP_BASIS_IRF, VP_BASIS_EXP_DECAY_IRF_PERIODIC = 9, 10, 11
@@ -56,6 +57,7 @@ ABI_SYMBOLS = [
     "vp_batch_create_external", "vp_set_params_with_basis", "vp_jacobian_with_derivatives", "vp_evaluate_with_basis",
     "vp_reduce_cost", "vp_fit_begin", "vp_fit_step_with_basis", "vp_fit_end", "vp_fit_active_set", "vp_global_statistics",
     "vp_set_bounds", "vp_search", "vp_set_irf", "vp_set_irf_period", "vp_set_weights", "vp_poisson_reweight",
+    "vp_robust_reweight", "vp_weights",
 ]
 
 
@@ -143,6 +145,9 @@ def load():
     if hasattr(lib, "vp_set_weights"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no re-weighting)
         lib.vp_set_weights.argtypes = [vp, vp, vp]
         lib.vp_poisson_reweight.argtypes = [vp, vp, C.c_int, C.c_double, vp, vp]
+    if hasattr(lib, "vp_robust_reweight"):  # (likewise)
+        lib.vp_robust_reweight.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_double, vp, vp]
+        lib.vp_weights.argtypes = [vp, vp]
     lib.vp_params.argtypes = [vp, vp]
     lib.vp_residuals.argtypes = [vp, vp, vp]
     lib.vp_jacobian.argtypes = [vp, vp, vp]

@@ -32,6 +32,9 @@ STATUS_OK, STATUS_NONFINITE, STATUS_NOT_EVALUATED = 0, 1, 2
 
 # fit_poisson: model-weighted rounds after the Neyman fit (measured on the CPU mirror)
 POISSON_ROUNDS = 9
+# fit_robust: re-weighted rounds after the fit at the base weights (measured on the CPU mirror)
+ROBUST_ROUNDS = 14
+ROBUST_LOSSES = {"huber": _lib.VP_ROBUST_HUBER, "cauchy": _lib.VP_ROBUST_CAUCHY, "tukey": _lib.VP_ROBUST_TUKEY}
 
 
 def _is_torch(a):
@@ -195,12 +198,16 @@ class BatchProblem:
         w = None
         if isinstance(weights, str):
             # Neyman weights of Poisson counts, w = 1/sqrt(max(y, 1)) per problem, formed where the data lives
-            if weights != "neyman":
-                raise ValueError("weights: an array, None or \"neyman\"")
+            # ("unit": per-problem unit weights, the base of a robust fit of homoscedastic data)
+            if weights not in ("neyman", "unit"):
+                raise ValueError("weights: an array, None, \"neyman\" or \"unit\"")
             if not self.single_rhs:
-                raise ValueError("weights=\"neyman\": weights are per problem, not per right-hand side (S = 1 only)")
-            one = Y.new_ones(()) if self.device_mode else self.np_dtype.type(1)
-            weights = 1.0 / (torch.sqrt(torch.maximum(Y, one)) if self.device_mode else np.sqrt(np.maximum(Y, one)))
+                raise ValueError("weights=\"%s\": weights are per problem, not per right-hand side (S = 1 only)" % weights)
+            if weights == "unit":
+                weights = torch.ones_like(Y) if self.device_mode else np.ones_like(Y)
+            else:
+                one = Y.new_ones(()) if self.device_mode else self.np_dtype.type(1)
+                weights = 1.0 / (torch.sqrt(torch.maximum(Y, one)) if self.device_mode else np.sqrt(np.maximum(Y, one)))
         if weights is not None:
             w = self._as_array(weights)
             if w.ndim == 2:
@@ -743,6 +750,93 @@ class BatchProblem:
         self.evaluate(a, want_residuals=False, want_jacobian=False)
         info = dict(deviance=dev, pearson=pear, reduced_deviance=dev / float(self.m - self.n - self.q), rounds=rounds)
         return a, Cm, rep, info
+
+    # ---- robust fits (vp_robust_reweight, vp_weights) ----
+    @_device_entry
+    def weights(self):
+        """the handle's current weights (vp_weights), (m,) or (B, m) as created; after ``robust_reweight`` /
+        ``fit_robust`` they are the outlier map of the fit (a weight far below its base weight marks an outlier)"""
+        if not self.weighted:
+            raise ValueError("weights: the handle was created without weights")
+        w = self._empty((self.B, self.m) if self.w_per_problem else (self.m,))
+        check(self.lib.vp_weights(self._h, self._ptr(w)))
+        return w
+
+    def _robust_arguments(self, loss, tuning, scale, what):
+        if loss not in ROBUST_LOSSES:
+            raise ValueError("%s: loss is \"huber\", \"cauchy\" or \"tukey\"" % what)
+        tuning = 0.0 if tuning is None else float(tuning)
+        if tuning != 0.0 and not (np.isfinite(tuning) and tuning > 0.0):
+            raise ValueError("%s: the tuning constant must be finite and > 0 (None: the 95 %% efficiency value)" % what)
+        scale = 0.0 if scale is None else float(scale)
+        if scale != 0.0 and not (np.isfinite(scale) and scale > 0.0):
+            raise ValueError("%s: the scale must be finite and > 0 (None: the normalised median of |e| per problem)" % what)
+        if not self.single_rhs:
+            raise ValueError("%s: weights are per problem, not per right-hand side (S = 1 only)" % what)
+        if not self.w_per_problem:
+            raise ValueError("%s: the handle needs per-problem weights (weights=\"unit\", \"neyman\" or a (B, m) array)" % what)
+        return ROBUST_LOSSES[loss], tuning, scale
+
+    def _checked_base_weights(self, w0, what):
+        if w0 is None:
+            return None
+        w0 = self._as_array(w0)
+        if tuple(w0.shape) != (self.B, self.m):
+            raise ValueError("%s: the base weights must have shape %r" % (what, (self.B, self.m)))
+        return w0
+
+    @_device_entry
+    def robust_reweight(self, Y, loss="huber", tuning=None, scale=None, base_weights=None):
+        """M-estimator weights from the residuals of the handle's current best fit, formed on the device
+        (vp_robust_reweight): w = w0 sqrt(omega(u)), u = w0 (y - f)/s, with omega of ``loss`` "huber", "cauchy" or "tukey"
+        and the tuning constant ``tuning`` (None: 1.345 / 2.385 / 4.685, 95 % efficiency on normal data).  ``scale`` None
+        estimates s per problem as 1.4826 times the median of |w0 (y - f)| over the rows with w0 != 0; a number fixes it
+        for the batch (the choice when w0 = 1/sigma is known).  ``base_weights`` (B, m) are w0 (None: 1) -- they should
+        make the residuals of the clean data homoscedastic (Neyman weights for counts: with unit weights on Poisson data
+        the median is set by the tail and the peak passes for an outlier) -- and are passed again every round, because
+        the handle's own weights are replaced.  Needs the fit of the current parameters (after ``fit`` / ``set_params``),
+        a single right-hand side and a handle with per-problem weights.  Cached results are invalidated, ``params()``
+        still returns the parameters.  Returns ``(scale, rho)``, both (B,) float64: s and sum rho(u) of the fit the weights
+        were formed from (NaN for a problem whose evaluation failed; its weights are kept)."""
+        loss, tuning, scale = self._robust_arguments(loss, tuning, scale, "robust_reweight")
+        Y = self._checked_observations(Y, "robust_reweight")
+        w0 = self._checked_base_weights(base_weights, "robust_reweight")
+        if not self._have_params:
+            raise ValueError("robust_reweight needs the fit of the current parameters (fit / set_params first)")
+        s, rho = self._empty((self.B,), np.float64), self._empty((self.B,), np.float64)
+        check(self.lib.vp_robust_reweight(self._h, self._ptr(Y), self._ptr(w0), loss, C.c_double(tuning), C.c_double(scale),
+                                          self._ptr(s), self._ptr(rho)))
+        self._have_params = False
+        return s, rho
+
+    def fit_robust(self, Y, alpha0, loss="huber", tuning=None, scale=None, rounds=ROBUST_ROUNDS, base_weights=None, solver=None):
+        """Robust (M-estimator) fit of Y (B, m) by iterated re-weighting -- not a Levenberg-Marquardt on rho: a fit at the
+        base weights from alpha0, then ``rounds`` times {``robust_reweight``, a fit from the previous parameters}, the
+        fixed point of which is the estimating equations sum psi(u_i) w0_i df_i/dtheta = 0.  One more re-weight and an
+        evaluation end it, so the returned ``(alpha, C, report, info)`` carries ``info = dict(scale, rho, rounds, weights)``
+        AT the returned point -- ``weights`` is the outlier map that belongs to it -- and the handle's state is that point
+        (``statistics()``, ``best_fit()`` need no further call).  ``statistics()`` is then the covariance of the weighted
+        least-squares problem at the final weights, not a sandwich estimator.  "huber" is convex; "tukey" and "cauchy" are
+        not and need a start from a sensible fit (alpha0 from a plain or a Huber fit).  ``base_weights`` None: unit weights;
+        see ``robust_reweight`` for what they should be.  ``rounds`` is a fixed count: a device-pointer handle makes no
+        host visit between the rounds, and torch tensors stay on the device throughout."""
+        rounds = int(rounds)
+        if rounds < 0:
+            raise ValueError("fit_robust: rounds >= 0")
+        self._robust_arguments(loss, tuning, scale, "fit_robust")
+        Y = self._checked_observations(Y, "fit_robust")
+        w0 = self._checked_base_weights(base_weights, "fit_robust")
+        if w0 is None:
+            w0 = torch.ones_like(Y) if self.device_mode else np.ones_like(Y)
+        self.set_weights(w0, Y)
+        a, Cm, rep = self.fit(alpha0, solver)
+        for _ in range(rounds):
+            self.robust_reweight(Y, loss, tuning, scale, w0)
+            a, Cm, rep = self.fit(a, solver)
+        # scale, rho and the weights of the returned (alpha, C); the evaluation makes the handle's state that alpha at them
+        s, rho = self.robust_reweight(Y, loss, tuning, scale, w0)
+        self.evaluate(a, want_residuals=False, want_jacobian=False)
+        return a, Cm, rep, dict(scale=s, rho=rho, rounds=rounds, weights=self.weights())
 
     @_device_entry
     def set_irf(self, irf):

@@ -398,6 +398,70 @@ class BatchProblem {
         r.pearson = std::move(g.pearson);
         return r;
     }
+    // the handle's current weights (vp_weights), m or B*m values as created; after robust_reweight / fit_robust the outlier map
+    std::vector<double> weights() {
+        if (!weighted_) throw std::invalid_argument("weights: the handle was created without weights");
+        std::vector<double> w((size_t)(w_per_problem_ ? B * m : m));
+        check(vp_weights(h_, w.data()));
+        return w;
+    }
+    // M-estimator weights from the residuals of the handle's current best fit, formed on the device (vp_robust_reweight):
+    // w = w0 sqrt(omega(u)), u = w0 (y - f)/s; loss VP_ROBUST_HUBER / _CAUCHY / _TUKEY, tuning 0 = the 95 % efficiency constant,
+    // scale 0 = the normalised median of |w0 (y - f)| per problem, base_weights null = 1 (they are passed again every round).
+    // Returns s and sum rho(u) of the fit the weights were formed from, [B] each
+    struct RobustScale {
+        std::vector<double> scale, rho;
+    };
+    RobustScale robust_reweight(const std::vector<double> &Y, int loss = VP_ROBUST_HUBER, double tuning = 0.0, double scale = 0.0,
+                                const std::vector<double> *base_weights = nullptr) {
+        if (loss != VP_ROBUST_HUBER && loss != VP_ROBUST_CAUCHY && loss != VP_ROBUST_TUKEY) throw std::invalid_argument("robust_reweight: unknown loss");
+        if (!(tuning >= 0.0) || !std::isfinite(tuning)) throw std::invalid_argument("robust_reweight: the tuning constant must be finite and > 0 (0: default)");
+        if (!(scale >= 0.0) || !std::isfinite(scale)) throw std::invalid_argument("robust_reweight: the scale must be finite and > 0 (0: estimated)");
+        if (S != 1) throw std::invalid_argument("robust_reweight: weights are per problem, not per right-hand side (S = 1 only)");
+        if (!w_per_problem_) throw std::invalid_argument("robust_reweight: the handle needs per-problem weights (B*m values)");
+        if ((int64_t)Y.size() != B * m) throw std::invalid_argument("Y must hold B*m values");
+        if (base_weights && (int64_t)base_weights->size() != B * m) throw std::invalid_argument("the base weights must hold B*m values");
+        RobustScale g;
+        g.scale.resize((size_t)B), g.rho.resize((size_t)B);
+        check(vp_robust_reweight(h_, Y.data(), base_weights ? base_weights->data() : nullptr, loss, tuning, scale, g.scale.data(),
+                                 g.rho.data()));
+        return g;
+    }
+    // Robust fit by iterated re-weighting, not an LM on rho (== the Python BatchProblem.fit_robust): a fit at the base weights
+    // from alpha0, `rounds` times {robust_reweight, fit from the previous parameters}, one more re-weight and an evaluation --
+    // scale, rho and the weights (the outlier map) belong to the returned point, which is the handle's state.  Tukey and
+    // Cauchy are not convex: start them from a sensible fit.  statistics() afterwards is the covariance of the weighted
+    // least-squares problem at the final weights, not a sandwich estimator.  The default `rounds` is measured: DESIGN.md 3j
+    struct RobustFit {
+        std::vector<double> alpha, C; // [B][q], [B][n]
+        std::vector<vp_report> report; // the last fit's
+        std::vector<double> scale, rho; // [B]
+        std::vector<double> weights; // [B][m]
+    };
+    static constexpr int kRobustRounds = 14;
+    RobustFit fit_robust(const std::vector<double> &Y, const std::vector<double> &alpha0, int loss = VP_ROBUST_HUBER,
+                         double tuning = 0.0, double scale = 0.0, int rounds = kRobustRounds,
+                         const std::vector<double> *base_weights = nullptr, const LevenbergMarquardt &solver = LevenbergMarquardt()) {
+        if (rounds < 0) throw std::invalid_argument("fit_robust: rounds >= 0");
+        const std::vector<double> unit(base_weights ? (size_t)0 : (size_t)(B * m), 1.0);
+        const std::vector<double> &w0 = base_weights ? *base_weights : unit;
+        RobustFit r;
+        r.alpha = alpha0;
+        r.report.resize((size_t)B);
+        r.C.resize((size_t)(B * n));
+        set_weights(w0, Y);
+        check(vp_fit(h_, &solver.o, r.alpha.data(), r.C.data(), r.report.data()));
+        for (int k = 0; k < rounds; ++k) {
+            robust_reweight(Y, loss, tuning, scale, &w0);
+            check(vp_fit(h_, &solver.o, r.alpha.data(), r.C.data(), r.report.data()));
+        }
+        RobustScale g = robust_reweight(Y, loss, tuning, scale, &w0);
+        check(vp_evaluate(h_, r.alpha.data(), nullptr, nullptr, nullptr, nullptr, nullptr));
+        r.scale = std::move(g.scale);
+        r.rho = std::move(g.rho);
+        r.weights = weights();
+        return r;
+    }
     // box bounds of fit() on a device-column handle (vp_set_bounds): q values (one box for all problems) or B*q values
     // each; +-INFINITY = unbounded on that side.  The bounds stay set until clear_bounds()
     void set_bounds(const std::vector<double> &lower, const std::vector<double> &upper) {

@@ -21,6 +21,7 @@
 #include "vp_cols.hpp"
 #include "vp_search.hpp"
 #include "vp_poisson.hpp"
+#include "vp_robust.hpp"
 
 using namespace vp;
 
@@ -2565,6 +2566,72 @@ int vp_poisson_reweight(vp_batch *h, const void *Y, int mode, double floor, doub
     if (int rc = pear.finish(h)) return rc;
     if (!device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream)); // the staged counts go out of scope
     return VP_ERR_OK;
+}
+
+// robust re-weighting on the device (vp_robust.hpp): the preconditions and the afterwards of vp_poisson_reweight in model mode
+int vp_robust_reweight(vp_batch *h, const void *Y, const void *w0, int loss, double tuning, double scale, double *scale_out,
+                       double *rho_out) {
+    VP_ENTER(h);
+    if (!Y) return fail(VP_ERR_INVALID, "vp_robust_reweight: null Y");
+    if (loss != VP_ROBUST_HUBER && loss != VP_ROBUST_CAUCHY && loss != VP_ROBUST_TUKEY)
+        return fail(VP_ERR_INVALID, "vp_robust_reweight: unknown loss");
+    if (!(tuning >= 0.0) || !std::isfinite(tuning))
+        return fail(VP_ERR_INVALID, "vp_robust_reweight: the tuning constant must be finite and > 0 (0: the 95 % efficiency value)");
+    if (!(scale >= 0.0) || !std::isfinite(scale))
+        return fail(VP_ERR_INVALID, "vp_robust_reweight: the scale must be finite and > 0 (0: the normalised median of |e| per problem)");
+    if (h->xf_running) return fail(VP_ERR_INVALID, "vp_robust_reweight during a stepped fit");
+    if (!h->d_w || !(h->flags & VP_FLAG_W_PER_PROBLEM))
+        return fail(VP_ERR_INVALID, "vp_robust_reweight: the handle must be created with VP_FLAG_W_PER_PROBLEM and a weights array");
+    if (h->S != 1)
+        return fail(VP_ERR_UNSUPPORTED, "vp_robust_reweight: weights are per problem, not per right-hand side (S = 1 only)");
+    if (h->m_user) return fail(VP_ERR_UNSUPPORTED, "vp_robust_reweight: not available on a handle padded for m < n");
+    if (!h->have_params) return fail(VP_ERR_INVALID, "vp_robust_reweight needs the fit of the current parameters (no parameters set yet)");
+    if (h->external && !h->ext_phi)
+        return fail(VP_ERR_INVALID, "vp_robust_reweight needs the columns of the handle's current parameters "
+                                    "(vp_set_params_with_basis at the fitted parameters first)");
+    if (!h->kern->best_fit) return fail(VP_ERR_UNSUPPORTED, "no best_fit kernel for this model");
+    static const double k95[3] = {1.345, 2.385, 4.685}; // 95 % efficiency at the normal distribution
+    const size_t bytes = (size_t)h->B * h->m * tsize(h->dtype);
+    InBuf y, base;
+    OutBuf sc, rho;
+    if (int rc = y.init(h, Y, bytes)) return rc;
+    if (int rc = base.init(h, w0, bytes)) return rc;
+    if (int rc = sc.init(h, scale_out, (size_t)h->B * sizeof(double))) return rc;
+    if (int rc = rho.init(h, rho_out, (size_t)h->B * sizeof(double))) return rc;
+    if (int rc = h->ensure(h->d_pfit, bytes)) return rc;
+    if (int rc = launch_best_fit(h, h->d_pfit)) return rc;
+    RobustParams p;
+    p.dtype = h->dtype;
+    p.Y = y.dptr;
+    p.F = h->d_pfit;
+    p.w0 = base.dptr;
+    p.status = h->d_status;
+    p.w = h->d_w;
+    p.yw = h->d_yw;
+    p.scale_out = (double *)sc.dptr;
+    p.rho_out = (double *)rho.dptr;
+    p.loss = loss;
+    p.k = tuning == 0.0 ? k95[loss] : tuning;
+    p.scale = scale;
+    p.m = (int)h->m;
+    p.B = h->B;
+    p.stream = h->stream;
+    if (int rc = robust_reweight_launch(p)) return fail(rc, "robust re-weighting kernel launch failed");
+    // the cached evaluation belongs to the old weights; the parameters stay (vp_params), the next vp_fit can start from them
+    const bool had_alpha = h->have_params || h->alpha_kept;
+    invalidate(h);
+    h->alpha_kept = had_alpha;
+    if (int rc = sc.finish(h)) return rc;
+    if (int rc = rho.finish(h)) return rc;
+    if (!device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream)); // the staged arrays go out of scope
+    return VP_ERR_OK;
+}
+
+int vp_weights(vp_batch *h, void *w_out) {
+    VP_ENTER(h);
+    if (!w_out) return fail(VP_ERR_INVALID, "vp_weights: null output");
+    if (!h->d_w) return fail(VP_ERR_INVALID, "vp_weights: the handle was created without weights");
+    return copy_out_rows(h, w_out, h->d_w, (h->flags & VP_FLAG_W_PER_PROBLEM) ? (size_t)h->B : (size_t)1);
 }
 
 int vp_statistics(vp_batch *h, void *cov_out, double *reduced_chi2_out, void *conf_sigma_out, int32_t *status) {
