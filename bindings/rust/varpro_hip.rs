@@ -125,6 +125,10 @@ extern "C" {
     pub fn vp_debug_registry_entry(index: i32, out: *mut i32) -> i32;
     /// which fit kernel the last fit launched: {kernel 0..5, padding variant 1 / 2 / 0 / -1, weighted, 0}
     pub fn vp_debug_last_fit(h: *mut vp_batch, out: *mut i32) -> i32;
+    /// what a global fit / evaluation (S > 1) launched: {factor waves, step waves, fit stream, eval stream, gx fit, gx eval, 0, 0}
+    pub fn vp_debug_last_global(h: *mut vp_batch, out: *mut i32) -> i32;
+    /// 1 / 0: entry `index` of the table of sets carries the multiple-right-hand-side kernels or not, < 0 past the end
+    pub fn vp_debug_registry_has_global(index: i32) -> i32;
     pub fn vp_summary(h: *mut vp_batch, out: *mut f64) -> i32;
     pub fn vp_summary_device(h: *mut vp_batch, dev_out4: *mut f64) -> i32;
     pub fn vp_global_fit_condition(h: *mut vp_batch, cond_out: *mut f64) -> i32;

@@ -86,6 +86,31 @@ int vp_debug_registry_entry(int index, int32_t out[8]);
  */
 int vp_debug_last_fit(vp_batch *h, int32_t out[4]);
 
+/*
+ * The counterpart for handles with several right-hand sides (global fits, S > 1): what the launchers of that path issued
+ * for the handle's vp_evaluate / vp_set_params / vp_residuals / vp_jacobian and vp_fit / vp_fit_trace calls so far, each
+ * field written by the launcher that issued the launch:
+ * out = { factor_waves, step_waves, fit_stream, eval_stream, gx_fit, gx_eval, 0, 0 }
+ *   factor_waves  waves per problem of the factor kernel of the last evaluation: 1 or 4; 0 = none yet (a fit factors inside
+ *                 its step kernel and leaves this field alone)
+ *   step_waves    waves per problem of the LM step kernel of the last fit: 1 or 4; 0 = no fit yet
+ *   fit_stream    the kernel of the fit's pass over the data columns, eval_stream that of the last evaluation:
+ *                 0 = none yet, 1 = mrhs_stream_kernel, 2 = mrhs_coop_dma_kernel, 3 = mrhs_coop_out_kernel with J,
+ *                 4 = mrhs_coop_out_kernel without J, 5 = the generic kernels (vp_generic.hpp)
+ *   gx_fit, gx_eval  workgroups per problem of that pass (0 with the generic kernels)
+ * A fit that replays a captured graph runs its launchers when the graph is captured, not when it is replayed: the record
+ * is then that of the capture, which took the same decisions (the graph is captured for this handle's shapes and re-captured
+ * when the options change).  A plain read: no GPU work, no state.
+ */
+int vp_debug_last_global(vp_batch *h, int32_t out[8]);
+
+/*
+ * Whether entry `index` of the table of registered sets carries the kernels of the multiple-right-hand-side path (factor,
+ * stream, LM step, finish), i.e. a handle with S > 1 can land on it: 1 / 0, VP_ERR_INVALID past the end of the table.
+ * Same index as vp_debug_registry_entry, whose record names the set.  No handle, no device.
+ */
+int vp_debug_registry_has_global(int index);
+
 #ifdef __cplusplus
 }
 #endif

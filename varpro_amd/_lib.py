@@ -63,7 +63,8 @@ ABI_SYMBOLS = [
 
 # test hooks (include/varpro_hip_debug.h): exported by the library, not part of the drop-in boundary
 DEBUG_SYMBOLS = ["vp_debug_gram_evaluate", "vp_debug_lmpar_gram", "vp_debug_set_refit", "vp_debug_set_column_fit",
-                 "vp_debug_search_ms", "vp_debug_kernel_set", "vp_debug_registry_entry", "vp_debug_last_fit"]
+                 "vp_debug_search_ms", "vp_debug_kernel_set", "vp_debug_registry_entry", "vp_debug_last_fit",
+                 "vp_debug_last_global", "vp_debug_registry_has_global"]
 
 
 class VarproHipUnavailable(ImportError):
@@ -171,6 +172,9 @@ def load():
         lib.vp_debug_registry_entry.argtypes = [C.c_int, i32p]
     if hasattr(lib, "vp_debug_last_fit"):
         lib.vp_debug_last_fit.argtypes = [vp, i32p]
+    if hasattr(lib, "vp_debug_last_global"):
+        lib.vp_debug_last_global.argtypes = [vp, i32p]
+        lib.vp_debug_registry_has_global.argtypes = [C.c_int]
     lib.vp_statistics.argtypes = [vp, vp, vp, vp, vp]
     lib.vp_global_statistics.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.vp_summary.argtypes = [vp, dp]
@@ -215,3 +219,10 @@ def registry_entries():
         if rc < 0:
             return out
         out.append((tuple(int(v) for v in rec), rc == 1))
+
+
+def registry_global_sets():
+    """test hook (vp_debug_registry_has_global): the records of the registered sets that carry the multiple-right-hand-side
+    kernels (vp_mrhs.hpp), in the order of the table.  Needs no GPU."""
+    lib = load()
+    return [rec for i, (rec, _single) in enumerate(registry_entries()) if lib.vp_debug_registry_has_global(i) == 1]

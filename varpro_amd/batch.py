@@ -625,6 +625,15 @@ class BatchProblem:
         check(self.lib.vp_debug_last_fit(self._h, rec))
         return tuple(int(v) for v in rec)
 
+    def last_global_launch(self):
+        """test hook (vp_debug_last_global): (factor_waves, step_waves, fit_stream, eval_stream, gx_fit, gx_eval, 0, 0) of the
+        launches the handle's global fits and evaluations (several right-hand sides) issued -- waves 1 or 4 per problem, 0 =
+        not launched yet; stream 0 = none yet, 1 = streaming kernel, 2 = cooperative DMA kernel, 3 / 4 = cooperative output
+        kernel with / without J, 5 = the generic kernels; gx workgroups per problem of that pass"""
+        rec = (C.c_int32 * 8)()
+        check(self.lib.vp_debug_last_global(self._h, rec))
+        return tuple(int(v) for v in rec)
+
     @_device_entry
     def best_fit(self):
         """== FitResult::best_fit (src/fit.rs:55-59, 87-91)"""

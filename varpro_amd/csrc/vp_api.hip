@@ -380,6 +380,7 @@ struct __attribute__((visibility("hidden"))) vp_batch {
     void *d_rescue_ws = nullptr; // kRescueBlocks workspace slots of the generic fit kernel
     int rescue_slot = 0;         // the counter the NEXT fit appends to
     int32_t last_fit[4] = {0, 0, 0, 0}; // vp_debug_last_fit: the record of the launcher that issued the last fit's launch
+    int32_t last_global[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // vp_debug_last_global: the records of the global-fit launchers
     bool rescue_off = false;     // vp_debug_set_refit(h, 0): fits keep the kernels' own `Numerical`
 };
 
@@ -563,6 +564,7 @@ void fill_params(vp_batch *h, LaunchParams &p) {
     p.ext_phi = h->ext_phi;
     p.ext_dphi = h->ext_dphi;
     p.ext_rows = (int)(h->m_user ? h->m_user : h->m);
+    p.last_global = h->last_global;
 }
 
 // the launch record of one step of the running reverse-communication fit (everything but where the trial points go)
@@ -2355,6 +2357,18 @@ int vp_debug_registry_entry(int index, int32_t out[8]) {
     const KernelEntry &e = registry()[(size_t)index];
     kernel_set_record(e, out);
     return e.stats && e.evaluate ? 1 : 0;
+}
+
+int vp_debug_last_global(vp_batch *h, int32_t out[8]) {
+    if (!h) return fail(VP_ERR_INVALID, "null handle");
+    if (!out) return fail(VP_ERR_INVALID, "null out");
+    for (int i = 0; i < 8; ++i) out[i] = h->last_global[i];
+    return VP_ERR_OK;
+}
+
+int vp_debug_registry_has_global(int index) {
+    if (index < 0 || (size_t)index >= registry().size()) return fail(VP_ERR_INVALID, "no such registry entry");
+    return has_mrhs_set(&registry()[(size_t)index]) ? 1 : 0;
 }
 
 int vp_debug_set_refit(vp_batch *h, int enabled) {

@@ -1244,6 +1244,7 @@ template <typename T> int launch_evaluate(const LaunchParams &p) {
     if (!fill_args(p, a) || !p.gen_ws) return VP_ERR_UNSUPPORTED;
     if (a.B <= 0) return VP_ERR_OK;
     const size_t lds = gen_lds_for<T>(a, &gen_evaluate_kernel<T>);
+    if (p.S > 1) record_global_stream(p, 1, kGlobalGeneric, 0);
     hipLaunchKernelGGL((gen_evaluate_kernel<T>), dim3((unsigned)p.gen_blocks), dim3(TB), lds, p.stream, a);
     return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
 }
@@ -1269,6 +1270,7 @@ template <typename T> int launch_mrhs_fit(const LaunchParams &p) {
     a.S_global = p.mrhs_S_global;
     if (a.phase != 0 && (!a.lm_state || !a.acc || !a.nactive)) return VP_ERR_INVALID;
     const size_t lds = gen_lds_for<T>(a, &gen_mrhs_fit_kernel<T>);
+    record_global_stream(p, 0, kGlobalGeneric, 0);
     hipLaunchKernelGGL((gen_mrhs_fit_kernel<T>), dim3((unsigned)p.gen_blocks), dim3(TB), lds, p.stream, a);
     return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
 }

@@ -96,6 +96,9 @@ struct LaunchParams {
                              // with the scaled re-fit built in re-fit what they flag themselves: nothing to launch afterwards)
     int32_t *last_fit;       // (host) [4], vp_debug_last_fit: written by the launcher that issues the fit launch -- {kernel,
                              // padding variant, weighted instantiation, 0}; null: nobody asked
+    int32_t *last_global;    // (host) [8], vp_debug_last_global: written by the launchers of the multiple-right-hand-side path
+                             // -- {factor waves, step waves, fit stream, evaluation stream, gx fit, gx evaluation, 0, 0}; null:
+                             // nobody asked
     const int32_t *gen_list; // generic fit kernel: fit the problems gen_list[2 + i], i < gen_list[gen_list_slot] (null: all B)
     int gen_list_slot;
     int gen_list_first;      // ... starting at entry gen_list_first (the ones before it were re-fitted by the set's own kernel)
@@ -111,6 +114,19 @@ inline void record_fit(const LaunchParams &p, int kernel, int padding, bool weig
     p.last_fit[1] = padding;
     p.last_fit[2] = weighted ? 1 : 0;
     p.last_fit[3] = 0;
+}
+
+// vp_debug_last_global's record: what the launchers of a global fit / evaluation issued (include/varpro_hip_debug.h)
+enum { kGlobalStream = 1, kGlobalCoopDma = 2, kGlobalCoopOutJ = 3, kGlobalCoopOut = 4, kGlobalGeneric = 5 };
+enum { kGlobalFactorWaves = 0, kGlobalStepWaves = 1 }; // (slots of the record)
+inline void record_global_waves(const LaunchParams &p, int slot, int waves) {
+    if (p.last_global) p.last_global[slot] = waves;
+}
+// mode: LaunchParams::mrhs_mode of the pass (0 = the fit's reduced sums, 1 = trait-level outputs)
+inline void record_global_stream(const LaunchParams &p, int mode, int code, int gx) {
+    if (!p.last_global) return;
+    p.last_global[mode == 0 ? 2 : 3] = code;
+    p.last_global[mode == 0 ? 4 : 5] = gx;
 }
 
 // workgroups of the fast re-fit launch (fit_kernel<..., RESCUE>, vp_fit.hpp): flagged problems beyond that go to the generic kernel

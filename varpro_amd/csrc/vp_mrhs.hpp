@@ -1413,12 +1413,15 @@ template <typename T, class M, int R> int launch_mrhs_factor(const LaunchParams 
     // lane spilled 596 VGPRs)
     if constexpr (R % 8 == 0) { // (R / 4 rows per lane, in pairs)
         if (a.B <= 1024 || mrhs_one_wave_spills<T, M, R>()) {
+            record_global_waves(p, kGlobalFactorWaves, 4);
             hipLaunchKernelGGL((mrhs_factor_kernel<T, M, R / 4, 4>), dim3((unsigned)a.B), dim3(256), 0, p.stream, a);
             return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
         }
     }
-    if constexpr (!(R % 8 == 0 && mrhs_one_wave_spills<T, M, R>()))
+    if constexpr (!(R % 8 == 0 && mrhs_one_wave_spills<T, M, R>())) {
+        record_global_waves(p, kGlobalFactorWaves, 1);
         hipLaunchKernelGGL((mrhs_factor_kernel<T, M, R, 1>), dim3((unsigned)a.B), dim3(64), 0, p.stream, a);
+    }
     return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
 }
 
@@ -1453,6 +1456,7 @@ template <typename T, class M, int R> int launch_mrhs_stream(const LaunchParams 
             constexpr int NWd = 4, RWd = R / NWd;
             const int gxo = mrhs_gx(p.S, 512);
             a.gx = gxo;
+            record_global_stream(p, p.mrhs_mode, a.J_out ? kGlobalCoopOutJ : kGlobalCoopOut, gxo);
             if (a.J_out)
                 hipLaunchKernelGGL((mrhs_coop_out_kernel<T, N, P, RWd, NWd, 2, 1>), dim3((unsigned)((int64_t)gxo * p.B)), dim3(64 * NWd), 0, p.stream, a);
             else
@@ -1468,6 +1472,7 @@ template <typename T, class M, int R> int launch_mrhs_stream(const LaunchParams 
             if (hipFuncSetAttribute((const void *)mrhs_coop_dma_kernel<T, N, P, RWd, NWd, NBd>,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds) != hipSuccess)
                 return VP_ERR_HIP;
+            record_global_stream(p, p.mrhs_mode, kGlobalCoopDma, gx);
             hipLaunchKernelGGL((mrhs_coop_dma_kernel<T, N, P, RWd, NWd, NBd>), dim3((unsigned)((int64_t)gx * p.B)), dim3(64 * NWd), dlds,
                                p.stream, a);
             return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
@@ -1478,6 +1483,7 @@ template <typename T, class M, int R> int launch_mrhs_stream(const LaunchParams 
     const int waves_per_wg = VP_MRHS_WAVES;
     dim3 grid((unsigned)((int64_t)gx * p.B)), block(64 * waves_per_wg);
     hipError_t e;
+    record_global_stream(p, p.mrhs_mode, kGlobalStream, gx);
     if (p.mrhs_mode == 0) {
         e = hipFuncSetAttribute((const void *)mrhs_stream_kernel<T, N, P, R, 0>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1521,12 +1527,15 @@ template <typename T, class M, int R> int launch_mrhs_lm(const LaunchParams &p) 
     // few problems: LM step and factorisation are pure latency -> 4 waves per problem (R/4 rows per lane)
     if constexpr (R % 8 == 0) { // (R / 4 rows per lane, in pairs)
         if (a.B <= 1024 || mrhs_one_wave_spills<T, M, R>()) {
+            record_global_waves(p, kGlobalStepWaves, 4);
             hipLaunchKernelGGL((mrhs_step_kernel<T, M, R / 4, 4>), dim3((unsigned)a.B), dim3(256), 0, p.stream, fa, a);
             return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
         }
     }
-    if constexpr (!(R % 8 == 0 && mrhs_one_wave_spills<T, M, R>()))
+    if constexpr (!(R % 8 == 0 && mrhs_one_wave_spills<T, M, R>())) {
+        record_global_waves(p, kGlobalStepWaves, 1);
         hipLaunchKernelGGL((mrhs_step_kernel<T, M, R, 1>), dim3((unsigned)p.B), dim3(64), 0, p.stream, fa, a);
+    }
     return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
 }
 
