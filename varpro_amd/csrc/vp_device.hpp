@@ -17,6 +17,8 @@
 
 // LDS-typed pointers (address space 3): accesses through them stay ds_* instructions in out-of-line functions
 #define VP_LDS __attribute__((address_space(3)))
+// global-memory pointers (address space 1): global_* instead of flat_* accesses wherever the pointer's origin is not visible
+#define VP_GLB __attribute__((address_space(1)))
 
 namespace vp {
 

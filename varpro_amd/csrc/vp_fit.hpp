@@ -1099,11 +1099,13 @@ template <typename T, class M> inline constexpr bool fit_rescue_v = M::kStatic &
 // Returns true when the fit ended on a Jacobian factor that is not finite after an evaluation that was ok (jac_not_finite)
 // and RESCUE is off -- the caller re-fits with RESCUE on (SELF) or the problem is on the handle's list (a.rescue).
 //   SELF: the caller re-fits a flagged problem itself: it is neither pushed to the list nor are its parameters stored
-template <typename T, class M, int R, int W, bool WEIGHTED, int PADM, bool RESCUE, bool SELF>
+//   GGRID: the shared grid is read from global memory (a.t, t_stride == 0; RowSource GMEM) -- s_t is not used and may be null
+template <typename T, class M, int R, int W, bool WEIGHTED, int PADM, bool RESCUE, bool SELF, bool GGRID = false>
 __device__ __forceinline__ bool fit_problem(const FitArgs<T, M> &a, const int64_t b, T *s_t, T *s_y, T *s_w, unsigned char *xch,
                                             LmState<T, M::N, M::Q> *st, const bool stage_grid) {
     static_assert(!(WEIGHTED && PADM != 0), "PADM is a unit-weight specialisation");
     static_assert(!RESCUE || fit_rescue_v<T, M>, "the scaled re-fit needs the constant-first sweep and diagonal pairs");
+    static_assert(!GGRID || !WEIGHTED, "global grid: unit weights");
     constexpr int N = M::N, P = M::P, Q = M::Q;
     // CF: the constant column leads the factorisation and is never materialised (evaluate_core_const_first)
     constexpr bool CF = M::kConstLast;
@@ -1119,7 +1121,7 @@ __device__ __forceinline__ bool fit_problem(const FitArgs<T, M> &a, const int64_
     // stage the problem's grid, weights and weighted data in LDS (row order, padding rows zero)
     {
         T tmp[R];
-        if (stage_grid) {
+        if (!GGRID && stage_grid) {
             const T *tp = a.t + b * a.t_stride;
             load_rows<T, R, W>(tp, m, lane, vec_aligned<T>(tp, m), tmp);
             store_rows<T, R, W>(s_t, MP, lane, true, tmp);
@@ -1142,9 +1144,9 @@ __device__ __forceinline__ bool fit_problem(const FitArgs<T, M> &a, const int64_
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     // the LDS copies are zero-padded to MP rows; valid rows are still i < m (scale 0 beyond)
-    using Src = RowSource<T, R, true, WEIGHTED ? 1 : 0, 1, W, true, PADM>;
+    using Src = RowSource<T, R, true, WEIGHTED ? 1 : 0, 1, W, true, PADM, false, false, GGRID>;
     Src src;
-    src.t = s_t;
+    src.t = GGRID ? a.t : s_t;
     src.w = s_w;
     src.m = m;
     src.lane = lane;
@@ -1274,7 +1276,8 @@ __device__ __forceinline__ bool fit_problem(const FitArgs<T, M> &a, const int64_
         if constexpr (RESCUE) {
             // largest exponent of exp(-t/tau_j) over the grid, from its two ends (grids are sorted; an unsorted one keeps ks = 0
             // and with it the unscaled result)
-            const T t_first = s_t[0], t_last = s_t[m - 1];
+            const T *tq = GGRID ? a.t : s_t;
+            const T t_first = tq[0], t_last = tq[m - 1];
 #pragma unroll
             for (int j = 0; j < N - 1; ++j) {
                 const T rt = T(1) / xt[j];

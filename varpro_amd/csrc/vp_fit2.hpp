@@ -151,6 +151,47 @@ template <typename T, typename TO = T> struct SlotConsts {
 #endif
 };
 
+// ONE-WAVE WORKGROUPS (W = 1; DESIGN.md section 3b, "One-wave workgroups").  A workgroup's LDS and wave slots return to the CU only
+// when its LAST wave ends, and the end of a launch is a few hundred waves each finishing one long fit: in a four-group workgroup
+// the three finished groups' share stays taken, and the next launch's workgroups (which need all four shares at once) wait.  With
+// one group per workgroup every wave hands back its registers and LDS the moment it ends.  What made that impossible was the
+// workgroup's LDS copy of the grid (one column: with eight of them per CU a slot column is lost, GS 2 -> 1 at the headline); the
+// one-wave workgroup reads the grid from global memory instead (RowSource GMEM: the same values, L1 / L2 resident, consumed by
+// build_columns only -- with unit weights the row scale never needs it) and holds nothing but its GS columns, records and constants.
+//   1 (on)  the full-length and last-pair variants (PADM 1, 2) of the W = 1 sets whose GS columns + records + constants fit a
+//           (4 WPS)-th of the CU's LDS: one group per workgroup, 64 threads, four times the workgroups; GS, the queue, the
+//           static assignment and the slots-or-waves decision are those of the four-group workgroup
+//   2       (A/B) the global-memory grid alone: the same sets keep their four-group workgroups, without the LDS grid
+//   0       the four-group workgroups with their LDS grid everywhere (the code before the switch, instruction for instruction)
+#ifndef VP_FIT2_WAVE_WG
+#define VP_FIT2_WAVE_WG 1
+#endif
+template <class TP> inline constexpr bool is_glb_ptr_v = false;
+template <class U> inline constexpr bool is_glb_ptr_v<VP_GLB U *> = true;
+// LDS of a slot workgroup: [the grid] + NG * GS columns + records + constants + pop words + exchange area (+ alignment slack)
+template <typename T, class M, int R, int W, int GS, int NG, bool GRID> constexpr size_t fit2_lds_bytes() {
+    return (size_t)64 * R * W * sizeof(T) * ((GRID ? 1 : 0) + (size_t)NG * GS) + (size_t)NG * GS * sizeof(SlotRec<T, M::N, M::Q>) +
+           sizeof(SlotConsts<T>) + (size_t)((GS + 3) / 4) * 4 * sizeof(int) + (size_t)group_xch_bytes<W>() + 16;
+}
+// the sets the switch applies to: W = 1, launched as slots at all (not the LDS exit of launch_fit2), and a one-wave workgroup
+// WITHOUT the grid fits its share of the CU
+template <typename T, class M, int R, int W, int GS, int WPS> constexpr bool fit2_wave_wg_fits() {
+    constexpr int BPC4 = (4 * WPS) / (W * 4) > 0 ? (4 * WPS) / (W * 4) : 1;
+    return W == 1 && fit2_lds_bytes<T, M, R, W, GS, 4, true>() <= (size_t)(160 * 1024) / BPC4 &&
+           fit2_lds_bytes<T, M, R, W, GS, 1, false>() <= (size_t)(160 * 1024) / (4 * WPS);
+}
+// does fit2_kernel<..., PADM, GS, NG, WPS> read the grid from global memory?  Not the general-length variant (PADM 0): there
+// every row pair can hold padding, the global source pays two bounds-checked element loads per pair where the zero-padded LDS
+// copy pays none, and the kernel spilled 207 VGPRs instead of 146 (219 with VP_JAC_Q2_NOCOPY) -- it keeps its workgroups
+template <typename T, class M, int R, int W, int PADM, int GS, int NG, int WPS> constexpr bool fit2_global_grid() {
+    return VP_FIT2_WAVE_WG != 0 && PADM != 0 && NG == 4 && fit2_wave_wg_fits<T, M, R, W, GS, WPS>();
+}
+// groups per workgroup the kernel RUNS with.  Its template argument NG stays the number everything else is computed for (GS, the
+// queue, the persistent grid): the kernels keep their names, and the launcher issues NG / fit2_groups() times the workgroups
+template <typename T, class M, int R, int W, int PADM, int GS, int NG, int WPS> constexpr int fit2_groups() {
+    return (VP_FIT2_WAVE_WG == 1 && fit2_global_grid<T, M, R, W, PADM, GS, NG, WPS>()) ? 1 : NG;
+}
+
 // Fill a slot: y' = H_0 y_w into the slot's LDS column (row order, zero padded); returns (H_0 y_w)[0].
 template <typename T, int R, class Src, class G>
 __device__ __forceinline__ T fill_slot_column(const T *__restrict__ yp, const int m, T *s_col, const Src &src,
@@ -187,8 +228,10 @@ __device__ __forceinline__ T fill_slot_column(const T *__restrict__ yp, const in
 
 // (Re)fill slot `s` of a wave with problem `prob` (wave-uniform; < 0 marks the slot empty).  Out of line: executed once
 // per fit, its register needs must not shape the allocation of the LM loop.
-template <typename T, int N, int Q, int R, int W, int PADM>
-__device__ VP_SLOT_FN void slot_fill(VP_LDS SlotRec<T, N, Q> *rec, VP_LDS T *s_col, VP_LDS const T *s_t,
+//   TP: where the grid is -- VP_LDS const T * (the workgroup's copy) or VP_GLB const T * (global memory, RowSource GMEM);
+//   the body, and below it the two out-of-line functions the kernel calls
+template <typename T, int N, int Q, int R, int W, int PADM, class TP>
+__device__ __forceinline__ void slot_fill_body(VP_LDS SlotRec<T, N, Q> *rec, VP_LDS T *s_col, TP s_t,
                                        VP_LDS const SlotConsts<T> *k, VP_LDS unsigned char *xch, const int prob,
                                        const T h0_beta, const T h0_u, const T h0_g) {
     using G = Grp<W>;
@@ -208,7 +251,7 @@ __device__ VP_SLOT_FN void slot_fill(VP_LDS SlotRec<T, N, Q> *rec, VP_LDS T *s_c
         if constexpr (W > 1) __syncthreads();
         return;
     }
-    using Src = RowSource<T, R, true, 0, 1, W, true, PADM>;
+    using Src = RowSource<T, R, true, 0, 1, W, true, PADM, false, false, is_glb_ptr_v<TP>>;
     Src src;
     src.t = (const T *)s_t;
     src.w = nullptr;
@@ -262,6 +305,18 @@ __device__ VP_SLOT_FN void slot_fill(VP_LDS SlotRec<T, N, Q> *rec, VP_LDS T *s_c
         rec->trow = 0;
     }
     if constexpr (W > 1) __syncthreads(); // column + record visible to all waves; exchange buffers quiescent again
+}
+template <typename T, int N, int Q, int R, int W, int PADM>
+__device__ VP_SLOT_FN void slot_fill(VP_LDS SlotRec<T, N, Q> *rec, VP_LDS T *s_col, VP_LDS const T *s_t,
+                                       VP_LDS const SlotConsts<T> *k, VP_LDS unsigned char *xch, const int prob,
+                                       const T h0_beta, const T h0_u, const T h0_g) {
+    slot_fill_body<T, N, Q, R, W, PADM>(rec, s_col, s_t, k, xch, prob, h0_beta, h0_u, h0_g);
+}
+template <typename T, int N, int Q, int R, int W, int PADM>
+__device__ VP_SLOT_FN void slot_fill(VP_LDS SlotRec<T, N, Q> *rec, VP_LDS T *s_col, VP_GLB const T *s_t,
+                                       VP_LDS const SlotConsts<T> *k, VP_LDS unsigned char *xch, const int prob,
+                                       const T h0_beta, const T h0_u, const T h0_g) {
+    slot_fill_body<T, N, Q, R, W, PADM>(rec, s_col, s_t, k, xch, prob, h0_beta, h0_u, h0_g);
 }
 
 // SCALAR phase: lane s runs the LM bookkeeping of slot s on its LDS record (trust-region update, accept / reject,
@@ -574,8 +629,8 @@ __device__ VP_SLOT_FN void slot_scalar_phase(VP_LDS SlotRec<T, N, Q> *recs, VP_L
 // finishing one long fit.  This function takes the slot's record and runs the REST of that fit the fit_kernel way:
 // same evaluation (the slot's H_0 y column), same arithmetic, results bit-identical to either kernel.  Out of line: its
 // register allocation must not touch the slot loop's.
-template <typename T, class M, int R, int PADM>
-__device__ VP_LONE_TAIL_LINKAGE void fit2_lone_tail(VP_LDS SlotRec<T, M::N, M::Q> *rec, VP_LDS const T *s_col, VP_LDS const T *s_t,
+template <typename T, class M, int R, int PADM, class TP>
+__device__ VP_LONE_TAIL_LINKAGE void fit2_lone_tail(VP_LDS SlotRec<T, M::N, M::Q> *rec, VP_LDS const T *s_col, TP s_t,
                                             VP_LDS const SlotConsts<T> *kc, const M mdl, const T eps, const int uniform,
                                             const T h0_beta, const T h0_u, const T h0_g) {
     constexpr int N = M::N, P = M::P, Q = M::Q;
@@ -583,7 +638,7 @@ __device__ VP_LONE_TAIL_LINKAGE void fit2_lone_tail(VP_LDS SlotRec<T, M::N, M::Q
     using G = SlotGrp<1>;
     G grp = G::make(nullptr);
     const int lane = grp.gl;
-    using Src = RowSource<T, R, true, 0, 1, 1, true, PADM>;
+    using Src = RowSource<T, R, true, 0, 1, 1, true, PADM, false, false, is_glb_ptr_v<TP>>;
     Src src;
     src.t = (const T *)s_t;
     src.w = nullptr;
@@ -917,12 +972,19 @@ template <typename T, class M, int R>
 __device__ VP_SLOT_FN void fit2_refit_flagged(const FitArgs<T, M> *a, const int64_t b, T *s_t, T *s_y, LmState<T, M::N, M::Q> *st) {
     (void)fit_problem<T, M, R, 1, false, 0, true, false>(*a, b, s_t, s_y, nullptr, nullptr, st, false);
 }
+// ... with the grid read from global memory (a->t): no s_t
+template <typename T, class M, int R>
+__device__ VP_SLOT_FN void fit2_refit_flagged_global(const FitArgs<T, M> *a, const int64_t b, T *s_y, LmState<T, M::N, M::Q> *st) {
+    (void)fit_problem<T, M, R, 1, false, 0, true, false, true>(*a, b, nullptr, s_y, nullptr, nullptr, st, false);
+}
 
 // A workgroup = NG groups of W waves (W = 1: NG = 4 independent waves; W > 1: ONE group, whose reductions use
 // workgroup barriers).  The groups share one LDS copy of the grid; each owns GS slots.  With W > 1 the scalar phase
 // runs on wave 0 of the group only -- the one-problem-per-group kernel has all W waves repeat the bookkeeping.
+// One-wave workgroups (VP_FIT2_WAVE_WG above; fit2_groups() == 1): no grid in LDS, workgroup barriers become the wave's.
 template <typename T, class M, int R, int W, int PADM, int GS, int NG, int WPS>
-__global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W * NG) / 4 : 1) fit2_kernel(const Fit2Args<T, M> args) {
+__global__ void __launch_bounds__((64 * W * fit2_groups<T, M, R, W, PADM, GS, NG, WPS>()), (WPS * W * NG) / 4 > 0 ? (WPS * W * NG) / 4 : 1)
+fit2_kernel(const Fit2Args<T, M> args) {
     static_assert(M::kConstLast && M::kDiagonalPairs, "slot kernel: multi-exponential + offset models");
     static_assert(W == 1 || NG == 1, "multi-wave groups synchronise with workgroup barriers: one group per workgroup");
     constexpr int N = M::N, P = M::P, Q = M::Q;
@@ -930,21 +992,25 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
     constexpr int YC = N - 1;  // data column
     constexpr int DC = YC + 1; // first derivative column
     constexpr int MP = 64 * R * W;
+    constexpr bool GG = fit2_global_grid<T, M, R, W, PADM, GS, NG, WPS>(); // the grid stays in global memory
+    constexpr int NGK = fit2_groups<T, M, R, W, PADM, GS, NG, WPS>();      // groups in this workgroup
+    constexpr bool WAVE = (W == 1 && NGK == 1);                       // the workgroup is this wave
+    constexpr int TP_ = GG ? 0 : MP;                                  // the grid's part of LDS
     using Rec = SlotRec<T, N, Q>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *s_t = reinterpret_cast<T *>(smem_raw);
     // group within the workgroup (wave-uniform: as a scalar, every LDS pointer derived from it is one too)
     const int gi = (W == 1) ? (VP_FIT2_SCALARS ? uni((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6)) : 0;
-    T *s_y = s_t + MP + (size_t)gi * GS * MP;
-    Rec *recs_all = reinterpret_cast<Rec *>(s_t + MP + (size_t)NG * GS * MP);
+    T *s_y = s_t + TP_ + (size_t)gi * GS * MP;
+    Rec *recs_all = reinterpret_cast<Rec *>(s_t + TP_ + (size_t)NGK * GS * MP);
     Rec *recs = recs_all + (size_t)gi * GS;
-    SlotConsts<T> *kc = reinterpret_cast<SlotConsts<T> *>(recs_all + (size_t)NG * GS);
+    SlotConsts<T> *kc = reinterpret_cast<SlotConsts<T> *>(recs_all + (size_t)NGK * GS);
     int *s_pop = reinterpret_cast<int *>(kc + 1);                                   // [GS] queue pops (W > 1)
     unsigned char *s_xch = reinterpret_cast<unsigned char *>(s_pop + ((GS + 3) / 4) * 4); // group exchange area (W > 1)
     using G = SlotGrp<W>;
     G grp = G::make(s_xch);
     const int lane = grp.gl; // group lane: row ownership
-    const int gw = (int)blockIdx.x * NG + gi; // persistent group index
+    const int gw = (int)blockIdx.x * NGK + gi; // persistent group index
     auto group_sync = [&]() __attribute__((always_inline)) {
         if constexpr (W > 1) {
             __syncthreads();
@@ -956,6 +1022,7 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
     T eps_;
     int m_, uniform_;
     int64_t B_;
+    VP_GLB const T *g_t = nullptr; // (GG) the handle's grid
     {
         const FitArgs<T, M> &a = args.f;
         // (the kernel's arguments live in memory -- the re-fit takes their address -- so what is read from them arrives in VGPRs)
@@ -964,9 +1031,13 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
         uniform_ = VP_FIT2_SCALARS ? uni(a.grid_uniform) : a.grid_uniform;
         B_ = VP_FIT2_SCALARS ? slot_uni((int64_t)a.B) : a.B;
         // ---- the shared grid (every group writes the same values: no ownership split needed) + the constants ----
-        T tmp[R];
-        load_rows<T, R, W>(a.t, m_, lane, vec_aligned<T>(a.t, m_), tmp);
-        store_rows<T, R, W>(s_t, MP, lane, true, tmp);
+        if constexpr (GG) {
+            g_t = (VP_GLB const T *)(VP_FIT2_SCALARS ? slot_uni((int64_t)(uintptr_t)a.t) : (int64_t)(uintptr_t)a.t);
+        } else {
+            T tmp[R];
+            load_rows<T, R, W>(a.t, m_, lane, vec_aligned<T>(a.t, m_), tmp);
+            store_rows<T, R, W>(s_t, MP, lane, true, tmp);
+        }
         if (threadIdx.x == 0) {
             kc->ftol = a.ftol;
             kc->xtol = a.xtol;
@@ -993,11 +1064,13 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
 #endif
         }
     }
-    __syncthreads();
+    if constexpr (WAVE) group_sync(); // (the workgroup is this wave: its own barrier)
+    else __syncthreads();
     const int m = m_;
-    using Src = RowSource<T, R, true, 0, 1, W, true, PADM>;
+    using Src = RowSource<T, R, true, 0, 1, W, true, PADM, false, false, GG>;
     Src src;
-    src.t = s_t;
+    if constexpr (GG) src.t = (const T *)g_t;
+    else src.t = s_t;
     src.w = nullptr;
     src.m = m;
     src.lane = lane;
@@ -1014,12 +1087,19 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
     }();
     const M mdl = args.f.mdl;
     if (threadIdx.x == 0) kc->pre_delta = src.uniform ? src.delta : T(0);
-    __syncthreads();
+    if constexpr (WAVE) group_sync(); // (the workgroup is this wave: its own barrier)
+    else __syncthreads();
 
     auto fill = [&](int s, int prob) __attribute__((always_inline)) {
-        slot_fill<T, N, Q, R, W, PADM>((VP_LDS Rec *)(recs + s), (VP_LDS T *)(s_y + (size_t)s * MP), (VP_LDS const T *)s_t,
-                                       (VP_LDS const SlotConsts<T> *)kc, (VP_LDS unsigned char *)s_xch, prob, h0.beta, h0.u,
-                                       h0.g);
+        if constexpr (GG) {
+            slot_fill<T, N, Q, R, W, PADM>((VP_LDS Rec *)(recs + s), (VP_LDS T *)(s_y + (size_t)s * MP), g_t,
+                                           (VP_LDS const SlotConsts<T> *)kc, (VP_LDS unsigned char *)s_xch, prob, h0.beta, h0.u,
+                                           h0.g);
+        } else {
+            slot_fill<T, N, Q, R, W, PADM>((VP_LDS Rec *)(recs + s), (VP_LDS T *)(s_y + (size_t)s * MP), (VP_LDS const T *)s_t,
+                                           (VP_LDS const SlotConsts<T> *)kc, (VP_LDS unsigned char *)s_xch, prob, h0.beta, h0.u,
+                                           h0.g);
+        }
         if constexpr (W > 1) grp.phase = 0; // slot_fill leaves the exchange buffers quiescent (barrier at its end)
     };
 
@@ -1195,9 +1275,14 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
 #pragma nounroll
             for (int s = 0; s < GS; ++s) {
                 if (uni(recs[s].prob) < 0) continue;
-                fit2_lone_tail<T, M, R, PADM>((VP_LDS Rec *)(recs + s), (VP_LDS const T *)(s_y + (size_t)s * MP),
-                                              (VP_LDS const T *)s_t, (VP_LDS const SlotConsts<T> *)kc, mdl, eps_, uniform_,
-                                              h0.beta, h0.u, h0.g);
+                if constexpr (GG) {
+                    fit2_lone_tail<T, M, R, PADM>((VP_LDS Rec *)(recs + s), (VP_LDS const T *)(s_y + (size_t)s * MP), g_t,
+                                                  (VP_LDS const SlotConsts<T> *)kc, mdl, eps_, uniform_, h0.beta, h0.u, h0.g);
+                } else {
+                    fit2_lone_tail<T, M, R, PADM>((VP_LDS Rec *)(recs + s), (VP_LDS const T *)(s_y + (size_t)s * MP),
+                                                  (VP_LDS const T *)s_t, (VP_LDS const SlotConsts<T> *)kc, mdl, eps_, uniform_,
+                                                  h0.beta, h0.u, h0.g);
+                }
             }
         }
     }
@@ -1221,7 +1306,8 @@ __global__ void __launch_bounds__(64 * W * NG, (WPS * W * NG) / 4 > 0 ? (WPS * W
         for (int i = 0; i < 2 * GS; ++i) {
             const int pb_ = dyn_get<2 * GS>(pend, i);
             if (pb_ < 0) continue;
-            fit2_refit_flagged<T, M, R>(&args.f, (int64_t)pb_, s_t, s_y, reinterpret_cast<LmState<T, N, Q> *>(recs));
+            if constexpr (GG) fit2_refit_flagged_global<T, M, R>(&args.f, (int64_t)pb_, s_y, reinterpret_cast<LmState<T, N, Q> *>(recs));
+            else fit2_refit_flagged<T, M, R>(&args.f, (int64_t)pb_, s_t, s_y, reinterpret_cast<LmState<T, N, Q> *>(recs));
         }
     }
 #ifdef VP_FIT2_CLOCKS
@@ -1245,6 +1331,9 @@ template <typename T, class M, int R, int W = 1> int launch_fit2(const LaunchPar
         constexpr int WPS = waves_for<T, R, M::N + M::P>();  // resident waves per SIMD
         constexpr int BPC = (4 * WPS) / (W * NG) > 0 ? (4 * WPS) / (W * NG) : 1; // workgroups per CU
         constexpr int GS = fit2_slots<T, R, W, NG, BPC, (int)sizeof(SlotRec<T, M::N, M::Q>)>();
+        // one-wave workgroups (VP_FIT2_WAVE_WG): a variant is launched with fit2_groups() groups per workgroup and NG / that
+        // times the workgroups; everything above and below -- GS, the slots-or-waves decision, the queue, the static assignment
+        // -- is computed for NG groups, so the launch hands out the same problems to the same group indices
         // fit_group: 0 = automatic, 1 = one problem per wave(-group) (fit_kernel), 2 = slots regardless of B.
         // Automatic, W = 1: a launch costs (work / throughput) + the latency of its slowest fit (~0.5 ms at m = 1024:
         // >100 LM evaluations of one problem, nothing to overlap them with).  The slot kernel has the higher
@@ -1293,16 +1382,22 @@ template <typename T, class M, int R, int W = 1> int launch_fit2(const LaunchPar
         args.queue = p.queue;
         args.waves_total = (int)(blocks * NG * W);
         if (hipMemsetD32Async((hipDeviceptr_t)p.queue, (int)(blocks * NG * GS), 1, p.stream) != hipSuccess) return VP_ERR_HIP;
-        const size_t lds = (size_t)64 * R * W * sizeof(T) * (1 + (size_t)NG * GS) + (size_t)NG * GS * sizeof(SlotRec<T, M::N, M::Q>) +
-                           sizeof(SlotConsts<T>) + (size_t)((GS + 3) / 4) * 4 * sizeof(int) + (size_t)group_xch_bytes<W>() + 16;
+        const size_t lds = fit2_lds_bytes<T, M, R, W, GS, NG, true>();
         // fit2_slots rounds a budget of less than one slot up to one; the workgroup then needs more than its share of the CU's
         // LDS.  ONE registered set is in that case and always takes this exit: the single exponential + offset at 32 fp64 rows
         // per lane (16 KiB per column, two workgroups per CU: 5 columns + records > 80 KiB) -- its three slot kernels are built
         // and never launched (tests/fit_cases.py: NO_ROOM_FOR_SLOTS; vp_debug_last_fit reports the wave kernel)
         if (lds > (size_t)(160 * 1024) / BPC) return launch_fit<T, M, R, W>(p);
+        // (the global-memory grid is read in 16-byte row pairs: the handle's own allocation always is aligned; a grid that is
+        // not runs on the wave kernel, which stages its grid element by element)
+        if (fit2_global_grid<T, M, R, W, 1, GS, NG, WPS>() && ((uintptr_t)p.t & 15u) != 0) return launch_fit<T, M, R, W>(p);
 #define VP_F2(PADM_)                                                                                                   \
-    hipLaunchKernelGGL((fit2_kernel<T, M, R, W, PADM_, GS, NG, WPS>), dim3((unsigned)blocks), dim3(64 * W * NG), lds,   \
-                       p.stream, args)
+    do {                                                                                                               \
+        constexpr int NGK = fit2_groups<T, M, R, W, PADM_, GS, NG, WPS>();                                             \
+        constexpr size_t lds_k = fit2_lds_bytes<T, M, R, W, GS, NGK, !fit2_global_grid<T, M, R, W, PADM_, GS, NG, WPS>()>(); \
+        hipLaunchKernelGGL((fit2_kernel<T, M, R, W, PADM_, GS, NG, WPS>), dim3((unsigned)(blocks * (NG / NGK))),        \
+                           dim3(64 * W * NGK), lds_k, p.stream, args);                                                 \
+    } while (0)
         if (p.m == 64 * R * W) {
             record_fit(p, kFitKernelSlots, 1, false);
             VP_F2(1);

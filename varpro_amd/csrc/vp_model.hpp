@@ -190,8 +190,12 @@ __device__ __forceinline__ void tsincos(float x, float &sn, float &cs) {
 //   TCALC  : (UNI, PADDED, unit weights) the grid values are COMPUTED, t = t(lane's first row pair) + k * delta,
 //            instead of loaded: 16 loads that the scheduler issues together are 32 live registers; the lattice is within
 //            4 ulp of the stored grid (grid_check_kernel)
+//   GMEM   : (PADDED, unit weights) `t` is the handle's m-row grid in GLOBAL memory (16-byte aligned, NOT padded) instead of a
+//            zero-padded LDS copy: the same row pairs through the same Layout, rows >= m read as 0 -- the values the LDS copy
+//            holds, so everything computed from them is bit-identical.  For kernels that cannot afford the LDS copy (the slot
+//            kernel's one-wave workgroups, vp_fit2.hpp); build_columns issues a lane's R loads together at its head
 template <typename T, int R, bool PADDED = false, int WMODE = 2, int VMODE = 2, int W = 1, bool RECUR = false,
-          int PADM = 0, bool UNI = false, bool TCALC = false>
+          int PADM = 0, bool UNI = false, bool TCALC = false, bool GMEM = false>
 struct RowSource {
     const T *t;  // grid, indexed by row (LDS or global)
     const T *w;  // weights indexed by row, or nullptr for unit weights
@@ -209,6 +213,8 @@ struct RowSource {
     static constexpr bool kAlwaysUniform = kRecur && UNI;
     // every row is valid and unweighted: the scale is the literal 1 and the recurrence needs no inf * 0 guard
     static constexpr bool kScaleOne = PADDED && WMODE == 0 && PADM == 1;
+    static constexpr bool kGlobal = GMEM;
+    static_assert(!GMEM || (PADDED && WMODE == 0 && !TCALC && L::VW == 2), "global grid: the unit-weight row-pair source");
     __device__ __forceinline__ void set_uniform(bool flag) {
         if constexpr (kRecur) {
             uniform = flag && m >= 3;
@@ -234,6 +240,33 @@ struct RowSource {
     __device__ __forceinline__ void get(int r0, T (&tt)[2], T (&sc)[2]) const {
         // r0 even (or R == 1): registers r0, r0+1 hold rows i, i+1
         const int i = L::row_of(r0, lane);
+        if constexpr (GMEM) {
+            typedef T v2_t __attribute__((ext_vector_type(2)));
+            // the grid pointer is wave-uniform: as a scalar base (+ a per-pair constant, SALU) with the lane's 32-bit byte offset,
+            // every access is base-register + offset-register addressing -- written as (lane pointer)[constant] the pairs
+            // beyond the instruction's 4 KiB immediate range each become a hoisted, i.e. spilled, 64-bit address
+            const uint64_t a0 = (uint64_t)(uintptr_t)t;
+            const VP_GLB char *gb = (const VP_GLB char *)(uintptr_t)(((uint64_t)(uint32_t)uni((int)(a0 >> 32)) << 32) |
+                                                                      (uint64_t)(uint32_t)uni((int)(uint32_t)a0));
+            // r0 is a compile-time constant after unrolling: only the pairs that can hold padding rows pay for the bounds
+            const bool maybe_pad = (PADM == 0) || (PADM == 2 && r0 >= R - L::VW);
+            if (!maybe_pad) { // rows i, i + 1 < m: one 16-byte access
+                const VP_GLB char *pb = gb + (size_t)(r0 / 2) * 64 * W * sizeof(v2_t);
+                const v2_t v = *(const VP_GLB v2_t *)(pb + (uint32_t)lane * (uint32_t)sizeof(v2_t));
+                tt[0] = v.x;
+                tt[1] = v.y;
+                sc[0] = sc[1] = T(1);
+            } else { // m may be odd and ends inside or before this pair: element accesses, out-of-range rows read t[0]
+                const bool in0 = i < m, in1 = i + 1 < m;
+                const T v0 = *(const VP_GLB T *)(gb + (uint32_t)(in0 ? i : 0) * (uint32_t)sizeof(T));
+                const T v1 = *(const VP_GLB T *)(gb + (uint32_t)(in1 ? i + 1 : 0) * (uint32_t)sizeof(T));
+                tt[0] = in0 ? v0 : T(0);
+                tt[1] = in1 ? v1 : T(0);
+                sc[0] = in0 ? T(1) : T(0);
+                sc[1] = in1 ? T(1) : T(0);
+            }
+            return;
+        }
         if constexpr (TCALC) {
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
@@ -303,6 +336,10 @@ struct RowSource {
     }
 };
 
+// (a source without kGlobal -- the caller-evaluated kernels' own sources -- reads no grid from global memory)
+template <class Src, class = void> struct row_source_global : std::false_type {};
+template <class Src> struct row_source_global<Src, std::void_t<decltype(Src::kGlobal)>> : std::integral_constant<bool, Src::kGlobal> {};
+
 // Build the (weighted) basis columns and derivative columns of one problem into the unified column
 // array C:  C[j] = W phi_j  (j < N),  C[N] is left alone (data column),  C[N+1+p] = W dphi_pair_p.
 //   DOFF: index of the first derivative column (N + 1 with a data column at N; N without one)
@@ -358,6 +395,21 @@ __device__ __forceinline__ void build_columns(const M &mdl, const T (&alpha)[M::
     // chain plus the grid's own deviation from the lattice, bounded at handle creation (grid_check_kernel);
     // the derivative columns still use the actual t_i.
     constexpr bool kRecur = Src::kRecur;
+    // a grid in global memory (RowSource GMEM): the lane's R values are requested HERE, in one burst, so that the first row
+    // pair's exponentials below run under their latency; the row loop consumes them pair by pair as it fills the columns
+    constexpr bool kGrid = row_source_global<Src>::value;
+    T tg[kGrid ? R : 1];
+    if constexpr (kGrid) {
+#pragma unroll
+        for (int r0 = 0; r0 < R; r0 += VW) {
+            T tt[2], sc[2];
+            src.get(r0, tt, sc);
+#pragma unroll
+            for (int e = 0; e < VW; ++e) tg[r0 + e] = tt[e];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    // (kGrid: src.get below gives the scales only -- its loads are dead -- and the grid values come from tg)
     T fu[N][VW], qq[N];
     // run-time-descriptor models: the trigonometric kinds advance by a ROTATION on a uniform grid -- exp(-a t) (cos b t + i sin b t)
     // of pair k is the value of pair k-1 times the wave-uniform w = exp(-a delta) (cos b delta + i sin b delta): 2 multiplies
@@ -376,6 +428,10 @@ __device__ __forceinline__ void build_columns(const M &mdl, const T (&alpha)[M::
                 static_assert(!PRE || M::kStatic, "precomputed trial-point scalars: static (multi-exponential) models");
                 T tt0[2], sc0[2];
                 src.get(0, tt0, sc0);
+                if constexpr (kGrid) {
+#pragma unroll
+                    for (int e = 0; e < VW; ++e) tt0[e] = tg[e];
+                }
                 T ax[N * VW], ex[N * VW];
 #pragma unroll
                 for (int j = 0; j < N; ++j) {
@@ -394,6 +450,10 @@ __device__ __forceinline__ void build_columns(const M &mdl, const T (&alpha)[M::
             } else if constexpr (kBatchExp) {
                 T tt0[2], sc0[2];
                 src.get(0, tt0, sc0);
+                if constexpr (kGrid) {
+#pragma unroll
+                    for (int e = 0; e < VW; ++e) tt0[e] = tg[e];
+                }
                 T ax[N * (VW + 1)], ex[N * (VW + 1)];
 #pragma unroll
                 for (int j = 0; j < N; ++j) {
@@ -454,6 +514,10 @@ __device__ __forceinline__ void build_columns(const M &mdl, const T (&alpha)[M::
                 if (r0 % VP_BUILD_CHUNK == 0 && r0 != 0) __builtin_amdgcn_sched_barrier(0);
             T tt[2], sc[2];
             src.get(r0, tt, sc);
+            if constexpr (kGrid) {
+#pragma unroll
+                for (int e = 0; e < VW; ++e) tt[e] = tg[r0 + e];
+            }
 #pragma unroll
             for (int j = 0; j < N; ++j) {
                 if constexpr (JSEL >= 0) {
