@@ -100,6 +100,14 @@ extern "C" {
     pub fn vp_weights(h: *mut vp_batch, w_out: *mut c_void) -> i32;
     /// box bounds of `vp_fit` on a device-column handle: host doubles `[q]` or `[B][q]`, infinite = unbounded, both null clears
     pub fn vp_set_bounds(h: *mut vp_batch, lower: *const f64, upper: *const f64, per_problem: i32) -> i32;
+    /// `vp_batch_create` with fixed nonlinear parameters: `fixed` `[q]` 0 / 1, `values` f64 `[q]` or `[B][q]` in the handle's
+    /// address space (entries of free parameters ignored).  The handle is the REDUCED model: every entry point sees the free
+    /// parameters only, in model order
+    pub fn vp_batch_create_fixed(h: *mut *mut vp_batch, model: *const vp_model_desc, dtype: i32, m: i64, s: i64, b: i64,
+        t: *const c_void, y: *const c_void, w: *const c_void, svd_epsilon: f64, flags: i32, device: i32,
+        hip_stream: *mut c_void, fixed: *const i32, values: *const f64, per_problem: i32) -> i32;
+    /// replace the fixed values between fits (same mask); only handles made by `vp_batch_create_fixed`
+    pub fn vp_set_fixed_values(h: *mut vp_batch, values: *const f64, per_problem: i32) -> i32;
     /// instrument response of a handle whose descriptor has an IRF kind: `[m]` or `[B][m]` in the handle's dtype and address
     /// space, copied by the handle; may be called again to replace it
     pub fn vp_set_irf(h: *mut vp_batch, irf: *const c_void, per_problem: i32) -> i32;

@@ -432,10 +432,42 @@ int vp_weights(vp_batch *h, void *w_out);
  * lower / upper: HOST pointers to doubles whatever the handle's dtype and flags, [q] (per_problem = 0) or [B][q];
  * -INFINITY / +INFINITY = unbounded on that side; both NULL clears the bounds.  Stays set across vp_fit calls and
  * vp_set_observations.
- * VP_ERR_INVALID: a NaN, lower >= upper (fixing a parameter is not supported), exactly one pointer NULL, a stepped fit in
- * progress.  VP_ERR_UNSUPPORTED: not a device-column handle (create it with VP_FLAG_DEVICE_COLUMNS).  A refusal leaves the
- * handle, and the bounds it had, as they were. */
+ * VP_ERR_INVALID: a NaN, lower >= upper (a parameter is fixed at creation: vp_batch_create_fixed), exactly one pointer
+ * NULL, a stepped fit in progress.  VP_ERR_UNSUPPORTED: not a device-column handle (create it with
+ * VP_FLAG_DEVICE_COLUMNS).  A refusal leaves the handle, and the bounds it had, as they were. */
 int vp_set_bounds(vp_batch *h, const double *lower, const double *upper, int per_problem);
+
+/*
+ * Fixed nonlinear parameters: "this parameter is known, do not fit it" (lmfit's vary=False, the "fix tau2" box of FLIM
+ * programs, a peak width set to the instrument's resolution).
+ *
+ * vp_batch_create_fixed takes everything vp_batch_create takes, plus
+ *   fixed        [q] int32, 0 (free) or 1 (fixed) per parameter of the descriptor;
+ *   values       [q] (per_problem = 0) or [B][q] DOUBLES whatever the handle's dtype, a host or device pointer according to
+ *                VP_FLAG_DEVICE_PTRS; entries of free parameters are ignored.  The handle copies them (on its stream);
+ *   per_problem  0: one set of values for the batch, 1: one per problem.
+ * It builds a device-column handle of ANY descriptor of the device kinds (kinds 0..4 alone become one as well, as under
+ * VP_FLAG_DEVICE_COLUMNS), and THE HANDLE IS THE REDUCED MODEL: from creation on every entry point sees a model of q_free
+ * parameters, the free ones in the descriptor's order -- vp_set_params, vp_evaluate, vp_fit, vp_params, vp_jacobian, vp_basis
+ * (dPhi: the pairs of free parameters only, in model order), vp_search (candidates [K][q_free]), vp_set_bounds ([q_free]
+ * boxes; they compose), vp_statistics / vp_global_statistics (cov [q_free][q_free]: the covariance of the problem that was
+ * solved) and the info queries.  Only the column kernels know the full parameter vector; the fit writes and factors fewer
+ * derivative columns.  A function whose parameters are all fixed has no derivative column and behaves like an invariant one.
+ * A mask of zeros is legal: an ordinary device-column handle in everything observable.
+ * A fixed value at which a column is not finite (a width 0, tau <= 0, a NaN) is NOT refused -- values may live on the device --
+ * and gives NaN columns, latched for that problem alone as for a parameter of that value.
+ * VP_ERR_INVALID: what vp_batch_create refuses, a null mask, a mask entry other than 0 or 1, every parameter fixed (no free
+ * parameter left; a descriptor without parameters and its empty mask are legal), null values when any parameter is fixed.  VP_ERR_UNSUPPORTED: a caller-evaluated descriptor (VP_BASIS_EXTERNAL).
+ *
+ * vp_set_fixed_values replaces the values between fits (same mask, same layout rules; copied on the handle's stream): the
+ * next point of a profile-likelihood scan.  Every cached evaluation / fit is invalidated.  VP_ERR_INVALID: null values on a
+ * handle with a fixed parameter.  VP_ERR_UNSUPPORTED: a handle that was not created by vp_batch_create_fixed.  The mask cannot
+ * change after creation.  (A stepped fit cannot be in progress on such a handle: vp_fit_begin refuses device-column handles.)
+ */
+int vp_batch_create_fixed(vp_batch **out, const vp_model_desc *model, int dtype, int64_t m, int64_t S, int64_t B, const void *t,
+                          const void *Y, const void *w, double svd_epsilon, int flags, int device, void *hip_stream,
+                          const int32_t *fixed, const double *values, int per_problem);
+int vp_set_fixed_values(vp_batch *h, const double *values, int per_problem);
 
 /* The instrument response of a handle whose descriptor contains VP_BASIS_EXP_DECAY_IRF / VP_BASIS_IRF (see "IRF
  * reconvolution" above).  irf: [m] (per_problem = 0) or [B][m], the handle's dtype, a host or device pointer according to

@@ -1,5 +1,7 @@
 """VGPRs / spilled VGPRs / scratch / LDS of every kernel in a built object or library (code-object metadata).
-usage: python tools/kernel_resources.py [varpro_amd/lib/libvarpro_hip.so] [--worst N] [--json out.json]"""
+usage: python tools/kernel_resources.py [varpro_amd/lib/libvarpro_hip.so] [--worst N] [--json out.json]
+       python tools/kernel_resources.py [library] --match SUBSTRING[,SUBSTRING...] [--json out.json]   every kernel whose symbol
+       contains one of the substrings, with its registers, spills and scratch"""
 import json, os, re, struct, subprocess, sys, tempfile, shutil
 LLVM = "/opt/rocm/lib/llvm/bin"
 
@@ -47,7 +49,7 @@ def kernel_notes(co):
 
 
 def main():
-    args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] not in ("--worst", "--json")]
+    args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] not in ("--worst", "--json", "--match")]
     obj = os.path.abspath(args[0] if args else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "varpro_amd", "lib", "libvarpro_hip.so"))
     worst = int(sys.argv[sys.argv.index("--worst") + 1]) if "--worst" in sys.argv else 15
     out_json = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else None
@@ -55,6 +57,15 @@ def main():
     try:
         cos = code_objects(obj, tmp)
         ks = [k for co in cos for k in kernel_notes(co)]
+        if "--match" in sys.argv:
+            subs = sys.argv[sys.argv.index("--match") + 1].split(",")
+            rows = sorted((dict(kernel=k["symbol"].replace(".kd", ""), vgpr_count=k["vgpr_count"], sgpr_count=k.get("sgpr_count", 0),
+                                vgpr_spill_count=k.get("vgpr_spill_count", 0), sgpr_spill_count=k.get("sgpr_spill_count", 0),
+                                private_segment_fixed_size=k.get("private_segment_fixed_size", 0))
+                           for k in ks if any(s in k.get("symbol", "") for s in subs)), key=lambda r: r["kernel"])
+            for r in rows: print("%3d VGPRs %3d SGPRs  %3d spilled  %4d B scratch  %s" % (r["vgpr_count"], r["sgpr_count"], r["vgpr_spill_count"], r["private_segment_fixed_size"], r["kernel"]))
+            if out_json: json.dump(dict(cmd="python tools/kernel_resources.py %s --match %s" % (os.path.relpath(obj), ",".join(subs)), kernels=rows), open(out_json, "w"), indent=1)
+            return
         def nm(k): return subprocess.run([shutil.which("c++filt") or "cat", k.get("symbol", k.get("name", "?")).replace(".kd", "")], capture_output=True, text=True).stdout.strip()[:150]
         sp = sorted(ks, key=lambda k: -k.get("vgpr_spill_count", 0))
         summary = {"object": os.path.relpath(obj), "bytes": os.path.getsize(obj), "compressed_bundles": open(obj, "rb").read().find(b"CCOB") >= 0,

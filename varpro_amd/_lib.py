@@ -57,7 +57,7 @@ ABI_SYMBOLS = [
     "vp_batch_create_external", "vp_set_params_with_basis", "vp_jacobian_with_derivatives", "vp_evaluate_with_basis",
     "vp_reduce_cost", "vp_fit_begin", "vp_fit_step_with_basis", "vp_fit_end", "vp_fit_active_set", "vp_global_statistics",
     "vp_set_bounds", "vp_search", "vp_set_irf", "vp_set_irf_period", "vp_set_weights", "vp_poisson_reweight",
-    "vp_robust_reweight", "vp_weights",
+    "vp_robust_reweight", "vp_weights", "vp_batch_create_fixed", "vp_set_fixed_values",
 ]
 
 
@@ -136,6 +136,10 @@ def load():
     lib.vp_set_observations.argtypes = [vp, vp]
     if hasattr(lib, "vp_set_bounds"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no bounds)
         lib.vp_set_bounds.argtypes = [vp, dp, dp, C.c_int]
+    if hasattr(lib, "vp_batch_create_fixed"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no fixed parameters)
+        lib.vp_batch_create_fixed.argtypes = [C.POINTER(vp), C.POINTER(ModelDesc), C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                              vp, vp, vp, C.c_double, C.c_int, C.c_int, vp, i32p, vp, C.c_int]
+        lib.vp_set_fixed_values.argtypes = [vp, vp, C.c_int]
     if hasattr(lib, "vp_set_irf"):  # (an older A/B build selected by VARPRO_HIP_LIBRARY has no IRF kinds)
         lib.vp_set_irf.argtypes = [vp, vp, C.c_int]
     if hasattr(lib, "vp_set_irf_period"):  # (... or no periodic IRF kind)

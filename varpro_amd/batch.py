@@ -139,8 +139,16 @@ def _device_entry(fn):
 
 
 class BatchProblem:
+    def __new__(cls, *args, **kwargs):
+        # fixed={...}: the subclass of varpro_amd/fixed.py keeps the books between the model's full parameter order and the
+        # handle's reduced one; without it nothing below takes another path
+        if cls is BatchProblem and kwargs.get("fixed") is not None:
+            from .fixed import FixedBatchProblem
+            return object.__new__(FixedBatchProblem)
+        return object.__new__(cls)
+
     def __init__(self, model, Y, x=None, weights=None, epsilon=None, device=0, grid_recurrence=True, stream_rows=False,
-                 device_columns=False, irf=None, irf_period=None):
+                 device_columns=False, irf=None, irf_period=None, *, fixed=None):
         """model: varpro_amd.SeparableModel; Y: (B, m) or (B, S, m); x: (m,) shared grid or (B, m)
         per-problem grids (default: model.x); weights: None (unit), (m,) or (B, m).
         irf: the instrument response of a model with ``basis.EXP_DECAY_IRF`` / ``basis.IRF``, (m,) shared or (B, m)
@@ -149,7 +157,10 @@ class BatchProblem:
         None or 0: the record is exactly one period.
         grid_recurrence=False sets VP_FLAG_NO_GRID_RECURRENCE (per-row exponentials even on uniform grids).
         device_columns=True sets VP_FLAG_DEVICE_COLUMNS: a descriptor of the exponential / trigonometric kinds alone becomes a
-        device-column handle too, which takes ``set_bounds``."""
+        device-column handle too, which takes ``set_bounds``.
+        fixed: dict parameter name -> value (a scalar, or a (B,) array / tensor: one value per problem) of nonlinear
+        parameters that are known and not fitted (vp_batch_create_fixed); the object is then a
+        ``varpro_amd.fixed.FixedBatchProblem``, whose docstring says what takes and returns the full parameter order."""
         self.lib = _lib.load()
         self.model = model
         self.n = model.base_function_count()
@@ -161,6 +172,11 @@ class BatchProblem:
         self.np_dtype = np.dtype(model.dtype)
         self.vp_dtype = _lib.VP_F64 if self.np_dtype == np.float64 else _lib.VP_F32
         self.external = hasattr(model, "ext_pairs")  # model.ExternalModel: the caller evaluates Phi / dPhi
+        if fixed is not None and self.external:
+            raise ValueError("fixed: a caller-evaluated model fixes its parameters in its own evaluation")
+        if fixed is not None and not hasattr(self, "_create_handle"):
+            raise ValueError("fixed: construct varpro_amd.BatchProblem itself, or derive from varpro_amd.fixed.FixedBatchProblem "
+                             "(a subclass of BatchProblem has none of its full-order bookkeeping)")
         x = model.x if x is None else x
         Y = self._as_array(Y)
         if Y.ndim == 2:
@@ -248,8 +264,12 @@ class BatchProblem:
                                                     stream))
         else:
             desc = model.desc()
-            check(self.lib.vp_batch_create(C.byref(h), C.byref(desc), self.vp_dtype, self.m, self.S, self.B,
-                                           self._ptr(x), self._ptr(Y), self._ptr(w), eps, flags, self.device, stream))
+            if fixed is not None:
+                self._fixed_arg = fixed
+                self._create_handle(h, desc, x, Y, w, eps, flags, stream)  # (fixed.py: vp_batch_create_fixed)
+            else:
+                check(self.lib.vp_batch_create(C.byref(h), C.byref(desc), self.vp_dtype, self.m, self.S, self.B,
+                                               self._ptr(x), self._ptr(Y), self._ptr(w), eps, flags, self.device, stream))
         self._h = h
         self._have_params = False  # mirrors the handle: set_params / evaluate / fit has run on the current data
         self._keep = None  # the handle owns copies (Y_w = W*Y, t, w)

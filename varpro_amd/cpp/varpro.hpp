@@ -294,6 +294,7 @@ inline double student_t_quantile(double p, double dof) {
 class BatchProblem {
     vp_batch *h_ = nullptr;
     bool weighted_ = false, w_per_problem_ = false; // created with weights / with one set per problem
+    int q_full_ = 0;                                // the descriptor's parameters (a handle with fixed ones: q counts the free)
 
   public:
     int64_t m = 0, S = 1, B = 0;
@@ -316,6 +317,36 @@ class BatchProblem {
                               epsilon, VP_FLAG_OWN_STREAM | (device_columns ? VP_FLAG_DEVICE_COLUMNS : 0) |
                                            (w_per_problem_ ? VP_FLAG_W_PER_PROBLEM : 0), device, nullptr));
     }
+    // Fixed nonlinear parameters (vp_batch_create_fixed): fixed[k] != 0 holds parameter k at values[k] (q values shared by
+    // the batch, or B*q values, one set per problem; entries of free parameters are ignored).  The handle is the REDUCED
+    // model: q counts the free parameters, and every method takes and returns them alone, in model order.
+    BatchProblem(const SeparableModel &model, const std::vector<double> &Y, int64_t B_, int64_t S_, const std::vector<int32_t> &fixed,
+                 const std::vector<double> &values, const std::vector<double> *weights = nullptr, double epsilon = -1.0,
+                 int device = 0) {
+        m = (int64_t)model.output_len();
+        B = B_;
+        S = S_;
+        n = model.desc.n_basis;
+        q_full_ = model.desc.n_params;
+        if ((int64_t)Y.size() != B * S * m) throw std::invalid_argument("Y must hold B*S*m values");
+        if ((int)fixed.size() != q_full_) throw std::invalid_argument("fixed must hold one entry per parameter");
+        q = 0;
+        for (int k = 0; k < q_full_; ++k) q += fixed[k] ? 0 : 1;
+        const bool per_problem = B > 1 && (int64_t)values.size() == B * q_full_;
+        if (q != q_full_ && (int64_t)values.size() != q_full_ && !per_problem) throw std::invalid_argument("values must hold q or B*q values");
+        weighted_ = weights != nullptr;
+        w_per_problem_ = weights && (int64_t)weights->size() == B * m && B > 1;
+        if (weights && (int64_t)weights->size() != m && !w_per_problem_) throw std::invalid_argument("weights must hold m or B*m values");
+        check(vp_batch_create_fixed(&h_, &model.desc, VP_F64, m, S, B, model.x.data(), Y.data(), weights ? weights->data() : nullptr,
+                                    epsilon, VP_FLAG_OWN_STREAM | (w_per_problem_ ? VP_FLAG_W_PER_PROBLEM : 0), device, nullptr,
+                                    fixed.data(), values.empty() ? nullptr : values.data(), per_problem ? 1 : 0));
+    }
+    // replace the fixed values between fits (vp_set_fixed_values): q_full or B*q_full values in the FULL parameter order
+    void set_fixed_values(const std::vector<double> &values) {
+        const bool per_problem = B > 1 && (int64_t)values.size() == B * q_full_;
+        if ((int64_t)values.size() != q_full_ && !per_problem) throw std::invalid_argument("values must hold q or B*q values");
+        check(vp_set_fixed_values(h_, values.data(), per_problem ? 1 : 0));
+    }
     // Neyman weights of Poisson counts, w = 1/sqrt(max(y, 1)): the `weights` of a handle that fit_poisson will drive
     static std::vector<double> neyman_weights(const std::vector<double> &counts) {
         std::vector<double> w(counts.size());
@@ -329,6 +360,7 @@ class BatchProblem {
         std::swap(h_, o.h_);
         m = o.m, S = o.S, B = o.B, n = o.n, q = o.q;
         weighted_ = o.weighted_, w_per_problem_ = o.w_per_problem_;
+        q_full_ = o.q_full_;
         return *this;
     }
     ~BatchProblem() {

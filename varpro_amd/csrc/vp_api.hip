@@ -354,6 +354,15 @@ struct __attribute__((visibility("hidden"))) vp_batch {
     // the longest record m dt_b of the batch (< 0: a device grid, the caller's contract)
     bool irf_periodic = false;
     double irf_period = 0.0, irf_span_max = -1.0;
+    // fixed nonlinear parameters (vp_batch_create_fixed): the handle is the REDUCED model -- q, p, the pair table and d_alpha
+    // are those of the free parameters in model order; col_model stays the full descriptor and only the column kernels'
+    // fixed siblings (vp_cols.hpp, vp_irf.hpp) read the map and the values
+    bool fixed = false;
+    int q_full = 0;
+    int32_t fix_src[VP_MAX_PARAMS] = {};   // full parameter k: its index in the free vector, < 0: fixed
+    void *d_fix_values = nullptr;          // [q_full] or [B][q_full] of the handle's dtype (sized for the per-problem form)
+    int64_t fix_stride = 0;                // 0: one set of values for all problems, q_full: per problem
+    void *d_inf_lo = nullptr, *d_inf_hi = nullptr; // [q]: the infinite box the siblings run with where the fit has none
     // batched reverse-communication LM fit of a caller-evaluated model (vp_fit_begin / vp_fit_step_with_basis / vp_fit_end)
     void *d_xf_state = nullptr;      // [B] LM records of the step kernel
     void *d_xf_trial = nullptr;      // [B][q] trial points of the last step
@@ -661,7 +670,18 @@ void fill_cols_params(const vp_batch *h, ColsParams &c) {
     c.irf_stride = h->irf_stride;
     c.irf_period = h->irf_period;
     c.stream = h->stream;
+    if (h->fixed) { // the fixed siblings: alpha over the free parameters, an infinite box unless the caller sets the fit's
+        c.fix_src = h->fix_src;
+        c.fix_values = h->d_fix_values;
+        c.fix_stride = h->fix_stride;
+        c.q_free = h->q;
+        c.lo = h->d_inf_lo;
+        c.hi = h->d_inf_hi;
+        c.bound_stride = 0;
+    }
 }
+// every column of the handle's descriptor: the column kernels, or their fixed siblings
+int handle_cols_fill(const ColsParams &c) { return c.fix_src ? cols_fill_fixed(c) : cols_fill(c); }
 // a handle with an IRF kind cannot evaluate a column before vp_set_irf
 #define VP_NEEDS_IRF(h, what)                                                                                          \
     if ((h)->irf_kinds && !(h)->have_irf)                                                                              \
@@ -691,7 +711,7 @@ int fill_own_columns(vp_batch *h, const void *alpha_dev, const int32_t *list, co
         c.bound_stride = h->bound_stride;
     }
     if (list) c.B = bound;
-    if (int rc = cols_fill(c)) return fail(rc, "column kernel launch failed");
+    if (int rc = handle_cols_fill(c)) return fail(rc, "column kernel launch failed");
     h->ext_phi = h->col_phi;
     h->ext_dphi = h->col_dphi;
     return 0;
@@ -1197,9 +1217,13 @@ struct ExtSpec {
     int np;
     const int32_t *pb, *pp;
 };
+// vp_batch_create_fixed: the mask over the descriptor's parameters (validated by the entry point)
+struct FixSpec {
+    const int32_t *fixed;
+};
 static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dtype, int64_t m, int64_t S, int64_t B,
                              const void *t, const void *Y, const void *w, double svd_epsilon, int flags, int device,
-                             void *hip_stream, bool data_on_device, const ExtSpec *ext);
+                             void *hip_stream, bool data_on_device, const ExtSpec *ext, const FixSpec *fix);
 
 // both create entry points.  m < n: the reference solves the underdetermined linear sub-problem by its truncated SVD
 // (minimum-norm coefficients, src/solvers/levmar/mod.rs:51-54).  Here: n - m extra rows of ZERO weight (grid value = the
@@ -1208,7 +1232,7 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
 // THEIR m rows (LaunchParams::ext_rows), the kernels read the missing rows as zeros.
 static int batch_create(vp_batch **out, const vp_model_desc *model, int dtype, int64_t m, int64_t S, int64_t B, const void *t,
                         const void *Y, const void *w, double svd_epsilon, int flags, int device, void *hip_stream,
-                        const ExtSpec *ext) {
+                        const ExtSpec *ext, const FixSpec *fix = nullptr) {
     const bool dev_data = (flags & VP_FLAG_DEVICE_PTRS) != 0;
     double irf_span_max = -1.0; // a host grid: the longest record m dt_b (vp_set_irf_period checks the period against it)
     if (model && !ext && model->n_basis > 0 && model->n_basis <= VP_MAX_BASIS && m == 1)
@@ -1237,7 +1261,7 @@ static int batch_create(vp_batch **out, const vp_model_desc *model, int dtype, i
     // (arguments batch_create_impl refuses go to it as they are, for its message)
     if (!out || !model || !Y || (!t && !ext) || m <= 0 || S <= 0 || B <= 0 || (dtype != VP_F64 && dtype != VP_F32) ||
         m >= model->n_basis || model->n_basis > VP_MAX_BASIS) {
-        const int rc = batch_create_impl(out, model, dtype, m, S, B, t, Y, w, svd_epsilon, flags, device, hip_stream, dev_data, ext);
+        const int rc = batch_create_impl(out, model, dtype, m, S, B, t, Y, w, svd_epsilon, flags, device, hip_stream, dev_data, ext, fix);
         if (rc == VP_ERR_OK && out && *out) (*out)->irf_span_max = irf_span_max;
         return rc;
     }
@@ -1253,7 +1277,7 @@ static int batch_create(vp_batch **out, const vp_model_desc *model, int dtype, i
     if (int rc = pad_inputs_host(pad, dev_data, st, tsize(dtype), m, model->n_basis, t, tb, Y, (size_t)B * S, w, wb, true))
         return rc;
     const int rc = batch_create_impl(out, model, dtype, model->n_basis, S, B, t ? pad.t.data() : nullptr, pad.y.data(),
-                                     pad.w.data(), svd_epsilon, flags, device, hip_stream, false, ext);
+                                     pad.w.data(), svd_epsilon, flags, device, hip_stream, false, ext, fix);
     if (rc == VP_ERR_OK) {
         (*out)->m_user = m;
         (*out)->irf_span_max = irf_span_max;
@@ -1265,6 +1289,101 @@ int vp_batch_create(vp_batch **out, const vp_model_desc *model, int dtype, int64
                     const void *t, const void *Y, const void *w, double svd_epsilon, int flags, int device,
                     void *hip_stream) {
     return batch_create(out, model, dtype, m, S, B, t, Y, w, svd_epsilon, flags, device, hip_stream, nullptr);
+}
+
+// ---- fixed nonlinear parameters (vp_batch_create_fixed / vp_set_fixed_values) ----------------------------------------------
+namespace {
+// the caller's doubles into the handle's dtype, one thread per entry
+__global__ void __launch_bounds__(256) fixed_values_kernel(const double *__restrict__ src, void *__restrict__ dst, const int dtype,
+                                                           const int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    if (dtype == VP_F64) static_cast<double *>(dst)[i] = src[i];
+    else static_cast<float *>(dst)[i] = (float)src[i];
+}
+// values [q_full] or [B][q_full] (host or device doubles, by the handle's flags) -> d_fix_values, on the handle's stream
+int store_fixed_values(vp_batch *h, const double *values, const int per_problem) {
+    bool any_fixed = false;
+    for (int k = 0; k < h->q_full; ++k) any_fixed = any_fixed || h->fix_src[k] < 0;
+    if (!any_fixed) return VP_ERR_OK; // (nothing reads them)
+    if (!values) return fail(VP_ERR_INVALID, "fixed parameters need their values: null values");
+    const int64_t total = (per_problem ? h->B : 1) * (int64_t)h->q_full;
+    InBuf v;
+    if (int rc = v.init(h, values, (size_t)total * sizeof(double))) return rc;
+    hipLaunchKernelGGL(fixed_values_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, (const double *)v.dptr,
+                       h->d_fix_values, h->dtype, total);
+    VP_HIP(hipGetLastError());
+    if (!device_ptrs(h)) VP_HIP(hipStreamSynchronize(h->stream)); // (the staging buffer goes out of scope)
+    h->fix_stride = per_problem ? h->q_full : 0;
+    return VP_ERR_OK;
+}
+} // namespace
+
+int vp_batch_create_fixed(vp_batch **out, const vp_model_desc *model, int dtype, int64_t m, int64_t S, int64_t B, const void *t,
+                          const void *Y, const void *w, double svd_epsilon, int flags, int device, void *hip_stream,
+                          const int32_t *fixed, const double *values, int per_problem) {
+    if (!out) return fail(VP_ERR_INVALID, "null output handle");
+    *out = nullptr;
+    if (!model) return fail(VP_ERR_INVALID, "null model");
+    if (model->n_basis <= 0 || model->n_basis > VP_MAX_BASIS || model->n_params < 0 || model->n_params > VP_MAX_PARAMS)
+        return fail(VP_ERR_INVALID, "model sizes out of range");
+    for (int j = 0; j < model->n_basis; ++j)
+        if (model->kind[j] == VP_BASIS_EXTERNAL)
+            return fail(VP_ERR_UNSUPPORTED, "vp_batch_create_fixed: a caller-evaluated model (VP_BASIS_EXTERNAL) fixes its "
+                                            "parameters in the caller's own evaluation");
+    if (!fixed) return fail(VP_ERR_INVALID, "vp_batch_create_fixed: null mask");
+    int n_fixed = 0;
+    for (int k = 0; k < model->n_params; ++k) {
+        if (fixed[k] != 0 && fixed[k] != 1) return fail(VP_ERR_INVALID, "vp_batch_create_fixed: a mask entry is 0 (free) or 1 (fixed)");
+        n_fixed += fixed[k];
+    }
+    // (a descriptor without nonlinear parameters and its empty mask: an all-zero mask like any other)
+    if (n_fixed > 0 && n_fixed == model->n_params) return fail(VP_ERR_INVALID, "vp_batch_create_fixed: no free parameter left");
+    if (n_fixed > 0 && !values) return fail(VP_ERR_INVALID, "vp_batch_create_fixed: fixed parameters need their values: null values");
+    const FixSpec fix{fixed};
+    if (int rc = batch_create(out, model, dtype, m, S, B, t, Y, w, svd_epsilon, flags, device, hip_stream, nullptr, &fix)) return rc;
+    vp_batch *h = *out;
+    auto setup = [&]() -> int {
+        DeviceGuard guard;
+        if (int rc = guard.enter(h->device)) return rc;
+        const size_t ts = tsize(h->dtype);
+        if (int rc = h->alloc(h->d_fix_values, std::max<size_t>((size_t)h->B * h->q_full, 1) * ts)) return rc;
+        // the infinite box: the identity of bound_map
+        if (int rc = h->alloc(h->d_inf_lo, std::max<size_t>((size_t)h->q, 1) * ts)) return rc;
+        if (int rc = h->alloc(h->d_inf_hi, std::max<size_t>((size_t)h->q, 1) * ts)) return rc;
+        double lo64[VP_MAX_PARAMS], hi64[VP_MAX_PARAMS];
+        float lo32[VP_MAX_PARAMS], hi32[VP_MAX_PARAMS];
+        for (int k = 0; k < VP_MAX_PARAMS; ++k) {
+            lo64[k] = -INFINITY, hi64[k] = INFINITY;
+            lo32[k] = -INFINITY, hi32[k] = INFINITY;
+        }
+        const bool f64 = h->dtype == VP_F64;
+        VP_HIP(hipMemcpyAsync(h->d_inf_lo, f64 ? (const void *)lo64 : (const void *)lo32, (size_t)h->q * ts, hipMemcpyHostToDevice, h->stream));
+        VP_HIP(hipMemcpyAsync(h->d_inf_hi, f64 ? (const void *)hi64 : (const void *)hi32, (size_t)h->q * ts, hipMemcpyHostToDevice, h->stream));
+        VP_HIP(hipStreamSynchronize(h->stream)); // (the staging arrays go out of scope)
+        return store_fixed_values(h, values, per_problem);
+    };
+    if (int rc = setup()) {
+        vp_batch_destroy(h);
+        *out = nullptr;
+        return rc;
+    }
+    return VP_ERR_OK;
+}
+
+int vp_set_fixed_values(vp_batch *h, const double *values, int per_problem) {
+    VP_ENTER(h);
+    if (!h->fixed)
+        return fail(VP_ERR_UNSUPPORTED, "vp_set_fixed_values: the handle was not created by vp_batch_create_fixed (the mask is part "
+                                        "of the handle's shape)");
+    // (defensive: vp_fit_begin is refused on device-column handles, which every fixed handle is, so no public call gets here)
+    if (h->xf_running) return fail(VP_ERR_INVALID, "vp_set_fixed_values during a stepped fit");
+    if (int rc = store_fixed_values(h, values, per_problem)) return rc;
+    // the cached evaluation / fit and the handle's columns belong to the old values
+    invalidate(h);
+    h->ext_phi = nullptr;
+    h->ext_dphi = nullptr;
+    return VP_ERR_OK;
 }
 
 // == SeparableProblemBuilder::build (src/problem/builder.rs:278-324) for a model the caller evaluates: any
@@ -1407,7 +1526,7 @@ static int batch_init(vp_batch *h, const void *t, const void *Y, const void *w, 
 
 static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dtype, int64_t m, int64_t S, int64_t B,
                              const void *t, const void *Y, const void *w, double svd_epsilon, int flags, int device,
-                             void *hip_stream, const bool data_on_device, const ExtSpec *ext) {
+                             void *hip_stream, const bool data_on_device, const ExtSpec *ext, const FixSpec *fix) {
     if (!out) return fail(VP_ERR_INVALID, "null output handle");
     *out = nullptr;
     if (!model) return fail(VP_ERR_INVALID, "null model");
@@ -1432,6 +1551,12 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
                 is_irf_kind(model->kind[j]))
                 devcols = true;
     if (!ext && (flags & VP_FLAG_DEVICE_COLUMNS)) devcols = true; // ... or any descriptor, on request (the kernel evaluates all kinds)
+    if (!ext && fix) devcols = true;                              // ... or with fixed parameters (vp_batch_create_fixed)
+    // fixed parameters: the inner shape is the reduced model -- the free parameters in model order and their pairs
+    int32_t fix_src[VP_MAX_PARAMS];
+    int q_free = 0;
+    for (int k = 0; k < VP_MAX_PARAMS; ++k) fix_src[k] = -1;
+    for (int k = 0; k < model->n_params; ++k) fix_src[k] = (fix && fix->fixed[k]) ? -1 : q_free++;
     vp_model_desc shape_desc;
     int32_t dc_pb[VP_MAX_PAIRS], dc_pp[VP_MAX_PAIRS];
     ExtSpec dc_ext{0, dc_pb, dc_pp};
@@ -1439,14 +1564,15 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
     if (devcols) {
         for (int j = 0; j < model->n_basis; ++j)
             for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k)
-                if (model->param[j][k] >= 0) {
+                if (model->param[j][k] >= 0 && fix_src[model->param[j][k]] >= 0) {
                     dc_pb[dc_ext.np] = j;
-                    dc_pp[dc_ext.np] = model->param[j][k];
+                    dc_pp[dc_ext.np] = fix_src[model->param[j][k]];
                     ++dc_ext.np;
                 }
+        npairs = dc_ext.np;
         std::memset(&shape_desc, 0, sizeof(shape_desc)); // (as vp_batch_create_external describes a caller-evaluated model)
         shape_desc.n_basis = model->n_basis;
-        shape_desc.n_params = model->n_params;
+        shape_desc.n_params = q_free;
         for (int j = 0; j < VP_MAX_BASIS; ++j) {
             shape_desc.kind[j] = j < model->n_basis ? VP_BASIS_EXTERNAL : 0;
             for (int a = 0; a < VP_MAX_BASIS_PARAMS; ++a) shape_desc.param[j][a] = -1;
@@ -1508,6 +1634,11 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
             if (is_irf_kind(descriptor->kind[j])) h->irf_kinds = true;
         for (int j = 0; j < descriptor->n_basis; ++j)
             if (descriptor->kind[j] == VP_BASIS_EXP_DECAY_IRF_PERIODIC) h->irf_periodic = true;
+        if (fix) {
+            h->fixed = true;
+            h->q_full = descriptor->n_params;
+            for (int k = 0; k < VP_MAX_PARAMS; ++k) h->fix_src[k] = fix_src[k];
+        }
     }
     if (int rc = batch_init(h, t, Y, w, hip_stream, data_on_device)) {
         vp_batch_destroy(h);
@@ -1871,7 +2002,7 @@ int vp_basis(vp_batch *h, const void *alpha, void *Phi_out, void *dPhi_out, int 
     if (!alpha) return fail(VP_ERR_INVALID, "null alpha");
     const size_t ts = tsize(h->dtype);
     if (h->devcols) { // the column kernel straight into the caller's arrays (host-pointer handles: staged)
-        const int nc = column_map(h->col_model, flags & VP_BASIS_SKIP_INVARIANT).n_phi_cols;
+        const int nc = column_map(h->col_model, flags & VP_BASIS_SKIP_INVARIANT).n_phi_cols; // (fixing changes no Phi column)
         const size_t rows = (size_t)col_rows(h);
         InBuf a;
         if (int rc = a.init(h, alpha, (size_t)h->B * h->q * ts)) return rc;
@@ -1886,7 +2017,7 @@ int vp_basis(vp_batch *h, const void *alpha, void *Phi_out, void *dPhi_out, int 
         c.skip_invariant = (flags & VP_BASIS_SKIP_INVARIANT) ? 1 : 0;
         c.nt = h->col_nt == 0 ? 0 : 1;
         Timer tm(h, VP_KERNEL_BASIS);
-        const int rc = cols_fill(c);
+        const int rc = handle_cols_fill(c);
         tm.stop();
         if (rc != VP_ERR_OK) return fail(rc, "column kernel launch failed");
         if (int rc2 = phi.finish(h)) return rc2;
@@ -2227,8 +2358,8 @@ int search_shared(vp_batch *h, const void *cand_dev, const int64_t K, SearchCloc
     c.t_stride = 0;
     c.alpha = cand_dev;
     c.phi = h->d_srch_phi;
-    c.B = K;
-    if (int rc = cols_fill(c)) return fail(rc, "column kernel launch failed");
+    c.B = K; // (the kernel's "problem" is the candidate: fixed values must be shared, vp_search sees to it)
+    if (int rc = handle_cols_fill(c)) return fail(rc, "column kernel launch failed");
     clk.mark();
     // zero columns beyond m and beyond K; every padded candidate marked, (b) clears the marks of the finite ones
     VP_HIP(hipMemsetAsync(h->d_srch_q, 0, (size_t)Kpad * h->n * ldq * ts, h->stream));
@@ -2294,7 +2425,8 @@ int vp_search(vp_batch *h, const void *cand, int64_t K, int flags, void *alpha_o
     // from here on the cached evaluation is being replaced
     h->r_valid = false;
     const bool shared = !per_problem && !(h->flags & (VP_FLAG_T_PER_PROBLEM | VP_FLAG_W_PER_PROBLEM)) && !h->m_user &&
-                        !(h->irf_kinds && h->irf_stride != 0); // (a response per problem: the candidate loop, like a grid per problem)
+                        !(h->irf_kinds && h->irf_stride != 0) && // (a response per problem: the candidate loop, like a grid per problem)
+                        !(h->fixed && h->fix_stride != 0);       // (fixed values per problem: the same)
     {
         SearchClock clk(h);
         if (shared) {

@@ -21,6 +21,14 @@
 // of the kernel reads u where the kernel reads alpha, forms alpha_k = g(u_k) per parameter (bound_map below: the MINUIT /
 // lmfit maps), evaluates the basis functions at alpha exactly as the unbounded kernel does and multiplies every stored
 // derivative column by dalpha_k/du_k of its parameter.  Nothing downstream of the columns knows about the bounds.
+//
+// Fixed parameters (vp_batch_create_fixed): the handle IS the reduced model -- its parameter vector holds the free
+// parameters only, in model order -- and only this kernel and the scan kernel know the full descriptor.  The fixed sibling
+// of the bounded kernel reads full parameter k through a map in its argument record: the free vector's entry src[k] (alpha,
+// or u of a bounded fit), or, src[k] < 0, the fixed value values[problem][k] -- indexed by the PROBLEM, not by the slot of
+// the active list.  Derivative columns are written for free parameters only and numbered by counting free pairs.  The
+// selection is uniform over the workgroup.  An unbounded fixed fit runs the sibling with an infinite box (the identity of
+// bound_map), so there is one fixed kernel per (dtype, store form), not two.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,20 +61,30 @@ struct ColsParams {
     int64_t irf_stride;    // 0: one response for all problems
     double irf_period;     // VP_BASIS_EXP_DECAY_IRF_PERIODIC: the period in grid units, 0: the record is one period
     hipStream_t stream;
+    // fixed parameters (vp_batch_create_fixed): `model` is the FULL descriptor, `alpha` (and lo / hi, which this form always
+    // needs: an infinite box where the fit has none) is [B][q_free] over the free parameters in model order
+    const int32_t *fix_src;  // host, [model.n_params]: index into the free vector, < 0: fixed; null: nothing is fixed
+    const void *fix_values;  // device, [model.n_params] or [B][fix_stride]: entries of free parameters are not read
+    int64_t fix_stride;      // 0: one set of values for all problems
+    int q_free;
 };
 // every column of the descriptor: cols_fill_kernel for the pointwise kinds, then the scan kernel for the IRF kinds
 int cols_fill(const ColsParams &p);
 int irf_cols_fill(const ColsParams &p); // the columns of the IRF kinds alone (vp_irf.hpp)
+// the same two for a record with fix_src (the fixed siblings: vp_inst_cols_fixed.hip)
+int cols_fill_fixed(const ColsParams &p);
+int irf_cols_fill_fixed(const ColsParams &p);
 inline bool is_irf_kind(const int kind) {
     return kind == VP_BASIS_EXP_DECAY_IRF || kind == VP_BASIS_IRF || kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC;
 }
 // the column numbering of a descriptor: phi_col[j] the Phi column of function j (-1: skipped, a VP_BASIS_CONST under
-// skip_invariant), first_pair[j] its first derivative column in dPhi (pairs in model order), and the totals
+// skip_invariant), first_pair[j] its first derivative column in dPhi (pairs in model order), and the totals.  fix_src
+// (ColsParams): only the pairs of free parameters have a column
 struct ColumnMap {
     int phi_col[VP_MAX_BASIS], first_pair[VP_MAX_BASIS];
     int n_phi_cols, n_pairs;
 };
-inline ColumnMap column_map(const vp_model_desc &model, const int skip_invariant) {
+inline ColumnMap column_map(const vp_model_desc &model, const int skip_invariant, const int32_t *fix_src = nullptr) {
     ColumnMap c;
     c.n_phi_cols = c.n_pairs = 0;
     for (int j = 0; j < VP_MAX_BASIS; ++j) {
@@ -75,7 +93,7 @@ inline ColumnMap column_map(const vp_model_desc &model, const int skip_invariant
         if (j >= model.n_basis) continue;
         if (!(skip_invariant && model.kind[j] == VP_BASIS_CONST)) c.phi_col[j] = c.n_phi_cols++;
         for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k)
-            if (model.param[j][k] >= 0) ++c.n_pairs;
+            if (model.param[j][k] >= 0 && !(fix_src && fix_src[model.param[j][k]] < 0)) ++c.n_pairs;
     }
     return c;
 }
@@ -100,6 +118,13 @@ template <typename T> struct ColsArgs {
 template <typename T> struct ColsBoundArgs : ColsArgs<T> {
     const T *lo, *hi;     // [q] or [B][bound_stride]; an infinite entry: no bound on that side
     int64_t bound_stride; // 0: shared
+};
+// the fixed kernel's record: `alpha`, lo and hi are [.][q_free] over the free parameters
+template <typename T> struct ColsFixedArgs : ColsBoundArgs<T> {
+    const T *values;               // [q] or [B][val_stride] over the FULL parameters
+    int64_t val_stride;            // 0: shared
+    int q_free;
+    int32_t src[VP_MAX_PARAMS];    // full parameter k: its index in the free vector, < 0: fixed
 };
 
 template <typename T> struct Vec;
@@ -247,7 +272,11 @@ __device__ __forceinline__ void basis_at(const int kind, const T t, const T p0, 
 // the body does change the unbounded kernels' instruction text (operands move) but not what they cost: registers, spills and
 // scratch are equal, the instruction count within one, the columns bit-equal and the device time of the fill and of a fit
 // inside the spread of the separate kernels' own rounds (profiles/cols_shared_body_*.json).
-template <typename T, bool VEC, bool NT, bool BND, typename Args> __device__ __forceinline__ void cols_fill_body(const Args &a) {
+// FIX (with BND): the fixed sibling -- a parameter comes from the free vector through a.src or from a.values, and only free
+// parameters have derivative columns.
+template <typename T, bool VEC, bool NT, bool BND, bool FIX = false, typename Args>
+__device__ __forceinline__ void cols_fill_body(const Args &a) {
+    static_assert(BND || !FIX, "the fixed sibling derives from the bounded body");
     constexpr int VW = Vec<T>::VW;
     const unsigned bpp = (unsigned)a.blocks_per_problem;
     const unsigned slot_local = blockIdx.x / bpp;
@@ -270,8 +299,12 @@ template <typename T, bool VEC, bool NT, bool BND, typename Args> __device__ __f
 #pragma unroll
         for (int e = 0; e < VW; ++e) tt[e] = tg[i + e < m ? e : 0];
     }
-    const int n = a.mdl.n_basis, q = a.mdl.n_params;
+    const int n = a.mdl.n_basis;
+    int q = a.mdl.n_params;
+    if constexpr (FIX) q = a.q_free;
     const T *al = a.alpha + b * q; // (BND: internal parameters)
+    const T *fv = nullptr;
+    if constexpr (FIX) fv = a.values + b * a.val_stride; // (b: the problem, also under an active list)
     const T *lo = nullptr, *hi = nullptr;
     if constexpr (BND) lo = a.lo + b * a.bound_stride, hi = a.hi + b * a.bound_stride;
     T *phi = a.phi ? a.phi + b * (int64_t)a.n_phi_cols * m : nullptr;
@@ -281,7 +314,19 @@ template <typename T, bool VEC, bool NT, bool BND, typename Args> __device__ __f
         const int kind = a.mdl.kind[j];
         const int i0 = a.mdl.param[j][0], i1 = a.mdl.param[j][1];
         T p0 = T(0), p1 = T(0), s0 = T(1), s1 = T(1); // s: dalpha/du
-        if constexpr (BND) {
+        bool free0 = i0 >= 0, free1 = i1 >= 0;        // the parameter has a derivative column
+        if constexpr (FIX) {
+            if (i0 >= 0) {
+                const int k0 = a.src[i0];
+                if (k0 >= 0) bound_map<T>(al[k0], lo[k0], hi[k0], p0, s0);
+                else p0 = fv[i0], free0 = false;
+            }
+            if (i1 >= 0) {
+                const int k1 = a.src[i1];
+                if (k1 >= 0) bound_map<T>(al[k1], lo[k1], hi[k1], p1, s1);
+                else p1 = fv[i1], free1 = false;
+            }
+        } else if constexpr (BND) {
             if (i0 >= 0) bound_map<T>(al[i0], lo[i0], hi[i0], p0, s0);
             if (i1 >= 0) bound_map<T>(al[i1], lo[i1], hi[i1], p1, s1);
         } else {
@@ -308,11 +353,11 @@ template <typename T, bool VEC, bool NT, bool BND, typename Args> __device__ __f
             }
         }
         if (phi && a.phi_col[j] >= 0) store_group<T, VEC, NT>(phi + (int64_t)a.phi_col[j] * m, i, m, f);
-        if (i0 >= 0) {
+        if (free0) {
             if (dphi) store_group<T, VEC, NT>(dphi + (int64_t)pair * m, i, m, d0);
             ++pair;
         }
-        if (i1 >= 0) {
+        if (free1) {
             if (dphi) store_group<T, VEC, NT>(dphi + (int64_t)pair * m, i, m, d1);
             ++pair;
         }
@@ -324,6 +369,10 @@ template <typename T, bool VEC, bool NT> __global__ void __launch_bounds__(256) 
 template <typename T, bool VEC, bool NT>
 __global__ void __launch_bounds__(256) cols_fill_bounded_kernel(const ColsBoundArgs<T> a) {
     cols_fill_body<T, VEC, NT, true>(a);
+}
+template <typename T, bool VEC, bool NT>
+__global__ void __launch_bounds__(256) cols_fill_fixed_kernel(const ColsFixedArgs<T> a) {
+    cols_fill_body<T, VEC, NT, true, true>(a);
 }
 
 // x <- g^-1(x) (INV) or x <- g(x), one thread per parameter of one problem
@@ -375,11 +424,21 @@ template <typename F> int launch_chunks(const int64_t B, const int64_t per_launc
     return VP_ERR_OK;
 }
 
-template <typename T> int launch_fill(const ColsParams &p) {
+// FIX: the record has fix_src -- the fixed sibling alone (its instantiations live in a unit of their own)
+template <typename T, bool FIX = false> int launch_fill(const ColsParams &p) {
     constexpr int VW = Vec<T>::VW;
     if (p.B <= 0 || p.m <= 0 || (!p.phi && !p.dphi)) return VP_ERR_OK;
-    ColsBoundArgs<T> a; // (the unbounded kernel takes its ColsArgs part)
-    const ColumnMap map = column_map(p.model, p.skip_invariant);
+    if (FIX && !(p.fix_src && p.fix_values && p.lo && p.hi)) return VP_ERR_INVALID;
+    std::conditional_t<FIX, ColsFixedArgs<T>, ColsBoundArgs<T>> a; // (the unbounded kernel takes its ColsArgs part)
+    const ColumnMap map = column_map(p.model, p.skip_invariant, FIX ? p.fix_src : nullptr);
+    if constexpr (FIX) {
+        a.values = (const T *)p.fix_values;
+        a.val_stride = p.fix_stride;
+        a.q_free = p.q_free;
+        for (int k = 0; k < VP_MAX_PARAMS; ++k) a.src[k] = k < p.model.n_params ? p.fix_src[k] : -1;
+    }
+    // the parameter has a derivative column
+    auto is_free = [&](const int k) { return k >= 0 && !(FIX && p.fix_src[k] < 0); };
     const int npairs = map.n_pairs;
     a.n_phi_cols = map.n_phi_cols;
     a.n_pairs = npairs;
@@ -403,19 +462,24 @@ template <typename T> int launch_fill(const ColsParams &p) {
         return launch_chunks(p.B, (int64_t)0x7fffffff / a.blocks_per_problem, [&](const int64_t first, const int64_t nb) {
             a.first = first;
             const dim3 grid((unsigned)(nb * a.blocks_per_problem)), block(256);
-            select_variant(
-                [&](auto V, auto N, auto BD) {
-                    if constexpr (BD.value) hipLaunchKernelGGL((cols_fill_bounded_kernel<T, V.value, N.value>), grid, block, 0, p.stream, a);
-                    else hipLaunchKernelGGL((cols_fill_kernel<T, V.value, N.value>), grid, block, 0, p.stream, static_cast<const ColsArgs<T> &>(a));
-                },
-                vec, p.nt != 0, bounded);
+            if constexpr (FIX) {
+                select_variant([&](auto V, auto N) { hipLaunchKernelGGL((cols_fill_fixed_kernel<T, V.value, N.value>), grid, block, 0, p.stream, a); },
+                               vec, p.nt != 0);
+            } else {
+                select_variant(
+                    [&](auto V, auto N, auto BD) {
+                        if constexpr (BD.value) hipLaunchKernelGGL((cols_fill_bounded_kernel<T, V.value, N.value>), grid, block, 0, p.stream, a);
+                        else hipLaunchKernelGGL((cols_fill_kernel<T, V.value, N.value>), grid, block, 0, p.stream, static_cast<const ColsArgs<T> &>(a));
+                    },
+                    vec, p.nt != 0, bounded);
+            }
         });
     };
     // The kernel numbers its derivative columns by counting the parameters of the functions it walks, so the functions of
     // the IRF kinds -- whose columns come from the scan kernel (vp_irf.hpp) -- are taken out of the descriptor it sees: a
     // VP_BASIS_IRF simply (it has no parameters), and at every VP_BASIS_EXP_DECAY_IRF[_PERIODIC] the descriptor is cut, the run of
     // functions behind it going to a launch of its own whose dPhi starts at that run's first pair.  A descriptor without
-    // these kinds is one run: the launch it always was.
+    // these kinds is one run: the launch it always was.  (FIX: first_pair counts the FREE pairs in front of the run.)
     a.mdl = p.model;
     int run = 0, run_pair0 = 0;
     bool stores = false; // the run has a column to write
@@ -441,7 +505,7 @@ template <typename T> int launch_fill(const ColsParams &p) {
         a.mdl.kind[run] = kind;
         for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k) a.mdl.param[run][k] = p.model.param[j][k];
         a.phi_col[run] = map.phi_col[j];
-        if ((a.phi && map.phi_col[j] >= 0) || (p.dphi && (p.model.param[j][0] >= 0 || p.model.param[j][1] >= 0))) stores = true;
+        if ((a.phi && map.phi_col[j] >= 0) || (p.dphi && (is_free(p.model.param[j][0]) || is_free(p.model.param[j][1])))) stores = true;
         ++run;
     }
     if (int rc = flush()) return rc;

@@ -58,6 +58,14 @@ template <typename T> struct IrfArgs {
     int m, q, n_phi_cols, n_pairs, nf;                        // nf: functions of the IRF kinds that have something to store
     int kind[VP_MAX_BASIS], phi_col[VP_MAX_BASIS], pair[VP_MAX_BASIS], param[VP_MAX_BASIS];
 };
+// the fixed sibling's record (vp_batch_create_fixed; vp_cols.hpp): `alpha`, lo, hi and q are those of the FREE vector, param[f]
+// indexes it and pair[f] counts free pairs -- unless the function's tau is fixed: then it comes from `values`, indexed by the
+// problem and the FULL parameter fixed_param[f], and the function has no derivative column
+template <typename T> struct IrfFixedArgs : IrfArgs<T> {
+    const T *values;      // [q_full] or [B][val_stride]
+    int64_t val_stride;   // 0: shared
+    int fixed_param[VP_MAX_BASIS]; // < 0: tau is free
+};
 
 __device__ __forceinline__ double texpm1(const double x) { return expm1(x); }
 __device__ __forceinline__ float texpm1(const float x) { return expm1f(x); }
@@ -88,8 +96,11 @@ __device__ __forceinline__ void load_group(const T *__restrict__ src, const int 
 // it costs them nothing: no kernel of the family needs more registers, spills or scratch than with a body of its own (14 need
 // 1 to 6 VGPRs fewer), the columns are bit-equal and the device time of the fill and of a fit lies inside the spread of the
 // separate kernels' own rounds (profiles/cols_shared_body_*.json).
-template <typename T, bool VEC, bool NT, bool BND, bool PER>
-__device__ __forceinline__ void irf_cols_body(const IrfArgs<T> &a, const T period) {
+// Args = IrfFixedArgs (with BND): the fixed sibling -- a fixed tau is read from a.values and has no derivative column.
+template <typename T, bool VEC, bool NT, bool BND, bool PER, typename Args>
+__device__ __forceinline__ void irf_cols_body(const Args &a, const T period) {
+    constexpr bool FIX = std::is_same<Args, IrfFixedArgs<T>>::value;
+    static_assert(BND || !FIX, "the fixed sibling derives from the bounded body");
     constexpr int VW = Vec<T>::VW, TILE = 64 * VW;
     const int lane = (int)(threadIdx.x & 63u);
     const unsigned wave = blockIdx.x * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -122,6 +133,14 @@ __device__ __forceinline__ void irf_cols_body(const IrfArgs<T> &a, const T perio
     const int pi = a.param[f];
     T tau = a.alpha[b * a.q + pi], dtau_du = T(1);
     if constexpr (BND) bound_map<T>(tau, a.lo[b * a.bound_stride + pi], a.hi[b * a.bound_stride + pi], tau, dtau_du);
+    if constexpr (FIX) {
+        // (wave-uniform: f is.  The loads above read entry 0 of the free vector and of the box for such a function)
+        if (a.fixed_param[f] >= 0) {
+            tau = a.values[b * a.val_stride + a.fixed_param[f]]; // (b: the problem, also under an active list)
+            dtau_du = T(1);
+            dphi = nullptr;
+        }
+    }
     if (!(tau > T(0))) tau = T(0) / T(0); // tau <= 0, NaN: not a decay -- NaN columns
     const T *tg = a.t + b * a.t_stride;
     const T dt = m > 1 ? (tg[m - 1] - tg[0]) / T(m - 1) : T(0);
@@ -228,14 +247,29 @@ __global__ void __launch_bounds__(256) irf_cols_periodic_kernel(const IrfArgs<T>
     irf_cols_body<T, VEC, NT, BND, true>(a, period);
 }
 
+template <typename T, bool VEC, bool NT>
+__global__ void __launch_bounds__(256) irf_cols_fixed_kernel(const IrfFixedArgs<T> a) {
+    irf_cols_body<T, VEC, NT, true, false>(a, T(0));
+}
+template <typename T, bool VEC, bool NT>
+__global__ void __launch_bounds__(256) irf_cols_periodic_fixed_kernel(const IrfFixedArgs<T> a, const T period) {
+    irf_cols_body<T, VEC, NT, true, true>(a, period);
+}
+
 // the columns of the IRF kinds: one launch of irf_cols_kernel over the functions of kinds 9 and 10, one of
 // irf_cols_periodic_kernel over those of kind 11 (a descriptor may mix them; the pairs are numbered over the whole descriptor)
-template <typename T> int launch_irf(const ColsParams &p) {
+// FIX: the record has fix_src -- the fixed siblings alone (their instantiations live in a unit of their own)
+template <typename T, bool FIX = false> int launch_irf(const ColsParams &p) {
     if (p.B <= 0 || p.m <= 0 || (!p.phi && !p.dphi)) return VP_ERR_OK;
     if (!p.irf) return VP_ERR_INVALID;
+    if (FIX && !(p.fix_src && p.fix_values && p.lo && p.hi)) return VP_ERR_INVALID;
     const bool vec = vec_groups<T>(p, p.irf, p.irf_stride), bounded = p.lo && p.hi;
-    const ColumnMap map = column_map(p.model, p.skip_invariant);
-    IrfArgs<T> a;
+    const ColumnMap map = column_map(p.model, p.skip_invariant, FIX ? p.fix_src : nullptr);
+    std::conditional_t<FIX, IrfFixedArgs<T>, IrfArgs<T>> a;
+    if constexpr (FIX) {
+        a.values = (const T *)p.fix_values;
+        a.val_stride = p.fix_stride;
+    }
     a.t = (const T *)p.t;
     a.alpha = (const T *)p.alpha;
     a.irf = (const T *)p.irf;
@@ -249,7 +283,7 @@ template <typename T> int launch_irf(const ColsParams &p) {
     a.irf_stride = p.irf_stride;
     a.bound_stride = p.bound_stride;
     a.m = p.m;
-    a.q = p.model.n_params;
+    a.q = FIX ? p.q_free : p.model.n_params;
     a.n_phi_cols = map.n_phi_cols;
     a.n_pairs = map.n_pairs;
     const T period = (T)p.irf_period;
@@ -264,22 +298,38 @@ template <typename T> int launch_irf(const ColsParams &p) {
             a.phi_col[nf] = map.phi_col[j];
             a.pair[nf] = map.first_pair[j];
             a.param[nf] = p.model.param[j][0];
+            if constexpr (FIX) { // (a VP_BASIS_IRF has no parameter: nothing is read for it)
+                const int k = p.model.param[j][0];
+                a.fixed_param[nf] = k >= 0 && p.fix_src[k] < 0 ? k : -1;
+                a.param[nf] = k >= 0 && p.fix_src[k] >= 0 ? p.fix_src[k] : 0;
+            }
             ++nf;
         }
         if (nf == 0) continue;
         for (int f = nf; f < VP_MAX_BASIS; ++f) a.kind[f] = a.phi_col[f] = a.pair[f] = a.param[f] = 0;
+        if constexpr (FIX)
+            for (int f = nf; f < VP_MAX_BASIS; ++f) a.fixed_param[f] = -1;
         a.nf = nf;
         // (4 waves per workgroup)
         const int rc = launch_chunks(p.B, (int64_t)0x7fffffff / nf, [&](const int64_t first, const int64_t nb) {
             a.first = first;
             a.slots = nb;
             const dim3 grid((unsigned)((nb * nf + 3) / 4)), block(256);
-            select_variant(
-                [&](auto V, auto N, auto BD, auto PER) {
-                    if constexpr (PER.value) hipLaunchKernelGGL((irf_cols_periodic_kernel<T, V.value, N.value, BD.value>), grid, block, 0, p.stream, a, period);
-                    else hipLaunchKernelGGL((irf_cols_kernel<T, V.value, N.value, BD.value>), grid, block, 0, p.stream, a);
-                },
-                vec, p.nt != 0, bounded, periodic != 0);
+            if constexpr (FIX) {
+                select_variant(
+                    [&](auto V, auto N, auto PER) {
+                        if constexpr (PER.value) hipLaunchKernelGGL((irf_cols_periodic_fixed_kernel<T, V.value, N.value>), grid, block, 0, p.stream, a, period);
+                        else hipLaunchKernelGGL((irf_cols_fixed_kernel<T, V.value, N.value>), grid, block, 0, p.stream, a);
+                    },
+                    vec, p.nt != 0, periodic != 0);
+            } else {
+                select_variant(
+                    [&](auto V, auto N, auto BD, auto PER) {
+                        if constexpr (PER.value) hipLaunchKernelGGL((irf_cols_periodic_kernel<T, V.value, N.value, BD.value>), grid, block, 0, p.stream, a, period);
+                        else hipLaunchKernelGGL((irf_cols_kernel<T, V.value, N.value, BD.value>), grid, block, 0, p.stream, a);
+                    },
+                    vec, p.nt != 0, bounded, periodic != 0);
+            }
         });
         if (rc) return rc;
     }

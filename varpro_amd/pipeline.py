@@ -19,20 +19,23 @@ except Exception:  # pragma: no cover
 
 class FitPipeline:
     def __init__(self, model, first_batch, x=None, weights=None, epsilon=None, n_slots=2, lower=None, upper=None,
-                 device_columns=False, irf=None):
+                 device_columns=False, irf=None, fixed=None):
         """first_batch: a torch CUDA tensor (B, m) or (B, S, m) that fixes the batch shape and the device;
         lower / upper: box bounds of every fit (BatchProblem.set_bounds), set on each slot's handle;
-        irf: the instrument response of a model with an IRF kind (BatchProblem.set_irf), copied into each slot's handle"""
+        irf: the instrument response of a model with an IRF kind (BatchProblem.set_irf), copied into each slot's handle;
+        fixed: nonlinear parameters held at known values in every fit (BatchProblem's ``fixed``; ``set_fixed`` replaces them)"""
         if torch is None or not isinstance(first_batch, torch.Tensor) or not first_batch.is_cuda:
             raise ValueError("FitPipeline works on torch CUDA tensors (device-pointer mode)")
         self.device = first_batch.device
         self.streams = [torch.cuda.Stream(device=self.device) for _ in range(int(n_slots))]
         self.slots = []
+        self._has_fixed = fixed is not None
+        extra = {} if fixed is None else {"fixed": fixed}
         for st in self.streams:
             st.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(st):
                 self.slots.append(BatchProblem(model, first_batch, x=x, weights=weights, epsilon=epsilon,
-                                               device_columns=device_columns, irf=irf))
+                                               device_columns=device_columns, irf=irf, **extra))
         self._k = 0
         if lower is not None or upper is not None:
             self.set_bounds(lower, upper)
@@ -42,6 +45,17 @@ class FitPipeline:
         it waits for each slot's stream)"""
         for h in self.slots:
             h.set_bounds(lower, upper)
+
+    def set_fixed(self, **values):
+        """the fixed values of the fits submitted from now on (FixedBatchProblem.set_fixed on every slot, each copy on its
+        slot's stream after the current stream's work).  ValueError: a pipeline created without ``fixed``"""
+        if not self._has_fixed:
+            raise ValueError("set_fixed: the pipeline was created without fixed= (the mask is part of each slot's handle)")
+        cur = torch.cuda.current_stream(self.device)
+        for h, st in zip(self.slots, self.streams):
+            st.wait_stream(cur)
+            with torch.cuda.stream(st):
+                h.set_fixed(**values)
 
     def set_irf(self, irf):
         """the instrument response of the fits submitted from now on (BatchProblem.set_irf on every slot, each copy on its
