@@ -336,6 +336,65 @@ __device__ __forceinline__ void solve_coeffs(const T (&Rm)[N][N], const T (&qty)
     truncated = true;
 }
 
+// The fast path of solve_coeffs WITHOUT its branches (the slot kernel's VP_FIT2_GRAM_ROUND 2, vp_fit2.hpp): the reciprocals,
+// R^-1, its squared Frobenius norm and the residual-corrected c are always computed, and the predicate the two branches of
+// solve_coeffs test is returned (per lane; the caller makes it uniform and calls solve_coeffs_truncated when it is false).  One
+// basic block, so the caller's reduction round can be scheduled into the chain.  The same operations on the same operands: where
+// the predicate holds c is solve_coeffs' c bit for bit; a zero diagonal only produces infinities and NaNs that are discarded.
+template <typename T, int N>
+__device__ __forceinline__ bool solve_coeffs_fast(const T (&Rm)[N][N], const T (&qty)[N], T eps, T (&c)[N]) {
+    bool zero_diag = false;
+#pragma unroll
+    for (int i = 0; i < N; ++i) zero_diag = zero_diag || (Rm[i][i] == T(0));
+    T d[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) d[i] = frcp(Rm[i][i]);
+    T inv_f2 = T(0);
+    T Ri[N][N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+#pragma unroll
+        for (int i = N - 1; i >= 0; --i) {
+            if (i > j) {
+                Ri[i][j] = T(0);
+                continue;
+            }
+            T acc = (i == j) ? T(1) : T(0);
+#pragma unroll
+            for (int l = i + 1; l <= j; ++l) acc = tfma(-Rm[i][l], Ri[l][j], acc);
+            Ri[i][j] = acc * d[i];
+            inv_f2 = tfma(Ri[i][j], Ri[i][j], inv_f2);
+        }
+    }
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i) {
+        T acc = qty[i];
+#pragma unroll
+        for (int j = i + 1; j < N; ++j) acc = tfma(-Rm[i][j], c[j], acc);
+        const T q0 = acc * d[i];
+        c[i] = tfma(tfma(-q0, Rm[i][i], acc), d[i], q0);
+    }
+    return !zero_diag && inv_f2 * eps * eps < T(1);
+}
+// ... and the other side of that predicate: solve_coeffs' call of truncated_solve
+template <typename T, int N>
+__device__ __forceinline__ void solve_coeffs_truncated(const T (&Rm)[N][N], const T (&qty)[N], T eps, T (&c)[N], T (&e)[N]) {
+    TruncIn<T, N> in;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        in.qty[i] = qty[i];
+#pragma unroll
+        for (int j = 0; j < N; ++j) in.Rm[i][j] = (j >= i) ? Rm[i][j] : T(0);
+    }
+    in.eps = eps;
+    const TruncOut<T, N> out = truncated_solve<T, N>(in);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        c[i] = out.c[i];
+        e[i] = out.e[i];
+    }
+}
+
 // Everything one evaluation produces that is wave-uniform.
 template <typename T, int N> struct EvalUniform {
     T c[N];   // linear coefficients
@@ -496,13 +555,26 @@ __device__ __forceinline__ void apply_qt(const T (&V)[NC][R], const T (&g)[N], T
 //   SHIFT: the derivative column of exponential j carries the factor 2^-ks[j] (build_columns); everything the basis
 //          columns produce (R, c, the residual) is the unshifted evaluation's bit for bit
 //   PRE:  1 / alpha_i and the recurrence ratios of the trial point come from the caller (build_columns)
-template <typename T, class M, int R, int NCX, class Src, class G, bool YPRE = false, bool NOD = false, bool SHIFT = false, bool PRE = false>
+//   GQ:   (the slot kernel's VP_FIT2_GRAM_ROUND, vp_fit2.hpp; models whose pair p is (basis p, parameter p)) the round that
+//         reduces ||r||^2 also carries the Gram values of the Jacobian's QR -- the Q (Q + 1) / 2 products Z_a . Z_b and the Q
+//         products Z_a . y over rows >= N, which jac_qrfac_scaled would reduce in a round of its own after the accept decision:
+//         both read only Q^T D_k and Q^T y, final once the last reflector is applied.  The same fma chains over the same
+//         registers in the same order as jac_qrfac_scaled's, behind the same masks (rows < N of the derivative columns are
+//         cleared IN PLACE here; rows < N of the data column count as 0, where jac_qrfac_scaled meets the e_k that
+//         residual_qcoords wrote there under a zero of the derivative column: fma(0, e, acc) = fma(0, 0, acc) = acc for every
+//         finite e, and a non-finite e makes fn2 non-finite -- ok false, the Gram values unused); the packed all-reduce gives a
+//         value the same tree at every position (vp_device.hpp).  gq[] receives them in jac_qrfac_scaled's order.
+//         2: as 1 with the linear solve as ONE basic block in front of the round (solve_coeffs_fast), its one branch behind it
+template <typename T, class M, int R, int NCX, class Src, class G, bool YPRE = false, bool NOD = false, bool SHIFT = false, bool PRE = false,
+          int GQ = 0>
 __device__ __forceinline__ void evaluate_core_const_first(const M &mdl, const T (&alpha)[M::Q], const Src &src, T eps,
                                                           G &grp, const ConstReflector<T> &h0, T (&C)[NCX][R],
                                                           EvalUniform<T, M::N> &u, SectionClock *clk = nullptr,
-                                                          const T qty0 = T(0), const int *ks = nullptr, const T *pre = nullptr) {
+                                                          const T qty0 = T(0), const int *ks = nullptr, const T *pre = nullptr,
+                                                          T *gq = nullptr) {
     constexpr int N = M::N, NE = M::N - 1;
     static_assert(M::kConstLast && NCX == M::N + (NOD ? 0 : M::P), "const-first sweep: N-1 exponentials + data + P derivatives");
+    static_assert(GQ == 0 || (!NOD && M::kDiagonalPairs && M::P == M::Q), "Gram round: one derivative column per parameter");
     using L = Layout<R, G::W>;
     constexpr int VW = L::VW;
     const int lane = grp.gl;
@@ -578,25 +650,90 @@ __device__ __forceinline__ void evaluate_core_const_first(const M &mdl, const T 
     }
     T cp[N];
     bool truncated;
-    chain_raise_scalar(grp); // (the triangular solve: one wave-uniform chain)
-    solve_coeffs<T, N>(Rm, qty, eps, cp, u.e, truncated);
+    T fn2;
+    if constexpr (GQ != 0) {
+        constexpr int QJ = M::Q, NGQ = QJ * (QJ + 1) / 2 + QJ;
+        auto solve = [&]() __attribute__((always_inline)) {
+            if constexpr (GQ == 2) {
+                truncated = !solve_coeffs_fast<T, N>(Rm, qty, eps, cp); // (per lane; made uniform behind the round)
+#pragma unroll
+                for (int i = 0; i < N; ++i) u.e[i] = T(0);
+            } else {
+                solve_coeffs<T, N>(Rm, qty, eps, cp, u.e, truncated);
+            }
+        };
+        // the partial sums of the round: [sum v^2 of the data column | Z_a . Z_b, a <= b | Z_a . y], rows >= N
+        T gr[1 + NGQ], yv[R];
+#pragma unroll
+        for (int k = 0; k < QJ; ++k)
+#pragma unroll
+            for (int r = 0; r < VW && r < R; ++r) C[NE + 1 + k][r] = (L::row_of(r, lane) < N) ? T(0) : C[NE + 1 + k][r];
+        {
+            T s = T(0);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                yv[r] = (r >= VW || L::row_of(r, lane) >= N) ? C[NE][r] : T(0);
+                s = tfma(yv[r], yv[r], s);
+            }
+            gr[0] = s;
+        }
+        int idx = 1;
+#pragma unroll
+        for (int a = 0; a < QJ; ++a)
+#pragma unroll
+            for (int b = a; b < QJ; ++b) {
+                T acc = T(0);
+#pragma unroll
+                for (int r = 0; r < R; ++r) acc = tfma(C[NE + 1 + a][r], C[NE + 1 + b][r], acc);
+                gr[idx++] = acc;
+            }
+#pragma unroll
+        for (int a = 0; a < QJ; ++a) {
+            T acc = T(0);
+#pragma unroll
+            for (int r = 0; r < R; ++r) acc = tfma(C[NE + 1 + a][r], yv[r], acc);
+            gr[idx++] = acc;
+        }
+        chain_raise(grp);
+        if constexpr (GQ == 2) solve();
+        group_allreduce(grp, gr);
+        chain_reduced(grp);
+        // (1: the solve BEHIND the round, which needs nothing from it.  In front of it -- the order of the two rounds -- the headline
+        // kernel spilled 17 VGPRs against 16 without the round; behind it 6)
+        if constexpr (GQ == 1) {
+            chain_raise_scalar(grp);
+            solve();
+        }
+        if constexpr (GQ == 2) {
+            truncated = uni(truncated);
+            if (truncated) solve_coeffs_truncated<T, N>(Rm, qty, eps, cp, u.e);
+        }
+        fn2 = gr[0];
+#pragma unroll
+        for (int i = 0; i < NGQ; ++i) gq[i] = gr[1 + i];
+    } else {
+        chain_raise_scalar(grp); // (the triangular solve: one wave-uniform chain)
+        solve_coeffs<T, N>(Rm, qty, eps, cp, u.e, truncated);
+    }
 #pragma unroll
     for (int j = 0; j < NE; ++j) u.c[j] = cp[1 + j];
     u.c[NE] = cp[0];
     u.g[0] = h0.g;
 #pragma unroll
     for (int j = 0; j < NE; ++j) u.g[1 + j] = g1[j];
-    chain_drop(grp);
-    // ||r||^2 = ||e||^2 + sum_{rows >= N} (Q^T y)^2
-    T s = T(0);
+    if constexpr (GQ == 0) {
+        chain_drop(grp);
+        // ||r||^2 = ||e||^2 + sum_{rows >= N} (Q^T y)^2
+        T s = T(0);
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const T v = (r >= VW || L::row_of(r, lane) >= N) ? C[NE][r] : T(0);
-        s = tfma(v, v, s);
+        for (int r = 0; r < R; ++r) {
+            const T v = (r >= VW || L::row_of(r, lane) >= N) ? C[NE][r] : T(0);
+            s = tfma(v, v, s);
+        }
+        chain_raise(grp);
+        fn2 = group_sum(grp, s);
+        chain_reduced(grp);
     }
-    chain_raise(grp);
-    T fn2 = group_sum(grp, s);
-    chain_reduced(grp);
 #pragma unroll
     for (int k = 0; k < N; ++k) fn2 = tfma(u.e[k], u.e[k], fn2);
     u.fn2 = fn2;

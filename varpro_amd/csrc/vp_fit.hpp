@@ -803,39 +803,50 @@ __device__ __forceinline__ void jac_q2_ordered(T (&Z)[2][R], T (&rv)[R], const T
 // uniform factors:  R_Z = R_G diag(s_perm),  acnorm_k = |s_k| ||g_k||,  pivoting by |s_k| * (downdated norm of g_k),
 // qtf unchanged.  Rows < ROW0 of G (the range(Q) part, not in P_perp) are cleared here.  MINPACK's "zero pivot column"
 // branch is taken on the SCALED norm (s_k == 0 makes z_k a zero column whatever g_k is).
-template <typename T, int R, int Q, int ROW0, class G>
+//   GIN: the Gram round has been done by the caller (evaluate_core_const_first GQ, vp_core.hpp: it travels with the reduction of
+//        ||r||^2): rows < ROW0 of Z are cleared already and gin[] holds the reduced [Z_a . Z_b, a <= b | Z_a . rv] in this
+//        routine's order -- no dot loops and no reduction round here, everything behind them as it is
+template <typename T, int R, int Q, int ROW0, class G, bool GIN = false>
 __device__ __forceinline__ void jac_qrfac_scaled(T (&Z)[Q][R], T (&rv)[R], const T (&s_in)[Q], T (&Rj)[Q][Q],
-                                                 T (&acnorm)[Q], int (&ipvt)[Q], T (&qtf)[Q], G &grp) {
+                                                 T (&acnorm)[Q], int (&ipvt)[Q], T (&qtf)[Q], G &grp, const T *gin = nullptr) {
     using L = Layout<R, G::W>;
     const int lane = grp.gl;
     T rdiag[Q], wa[Q], sa[Q], sc[Q]; // rdiag/wa: norms of the UNSCALED columns; sa = |s|; sc = s (follow the columns)
     T Gm[Q][Q], bz[Q];
+    if constexpr (!GIN) {
 #pragma unroll
-    for (int k = 0; k < Q; ++k)
+        for (int k = 0; k < Q; ++k)
 #pragma unroll
-        for (int r = 0; r < L::VW && r < R; ++r) Z[k][r] = (L::row_of(r, lane) < ROW0) ? T(0) : Z[k][r];
+            for (int r = 0; r < L::VW && r < R; ++r) Z[k][r] = (L::row_of(r, lane) < ROW0) ? T(0) : Z[k][r];
+    }
     {
         constexpr int NG = Q * (Q + 1) / 2 + Q;
         T gr[NG];
         int idx = 0;
+        if constexpr (GIN) {
 #pragma unroll
-        for (int a = 0; a < Q; ++a)
+            for (int i = 0; i < NG; ++i) gr[i] = gin[i];
+            if constexpr (Q == 2 && VP_JAC_Q2_NOSWAP) chain_raise(grp); // (as below: jac_q2_ordered's broadcast runs raised)
+        } else {
 #pragma unroll
-            for (int b = a; b < Q; ++b) {
+            for (int a = 0; a < Q; ++a)
+#pragma unroll
+                for (int b = a; b < Q; ++b) {
+                    T acc = T(0);
+#pragma unroll
+                    for (int r = 0; r < R; ++r) acc = tfma(Z[a][r], Z[b][r], acc);
+                    gr[idx++] = acc;
+                }
+#pragma unroll
+            for (int a = 0; a < Q; ++a) {
                 T acc = T(0);
 #pragma unroll
-                for (int r = 0; r < R; ++r) acc = tfma(Z[a][r], Z[b][r], acc);
+                for (int r = 0; r < R; ++r) acc = tfma(Z[a][r], rv[r], acc);
                 gr[idx++] = acc;
             }
-#pragma unroll
-        for (int a = 0; a < Q; ++a) {
-            T acc = T(0);
-#pragma unroll
-            for (int r = 0; r < R; ++r) acc = tfma(Z[a][r], rv[r], acc);
-            gr[idx++] = acc;
+            if constexpr (Q == 2 && VP_JAC_Q2_NOSWAP) chain_raise(grp); // (held through jac_q2_ordered's broadcast; only that path has the helpers)
+            group_allreduce(grp, gr);
         }
-        if constexpr (Q == 2 && VP_JAC_Q2_NOSWAP) chain_raise(grp); // (held through jac_q2_ordered's broadcast; only that path has the helpers)
-        group_allreduce(grp, gr);
         idx = 0;
 #pragma unroll
         for (int a = 0; a < Q; ++a)

@@ -88,6 +88,27 @@ template <typename T, int N, int Q> struct alignas(8) SlotRec {
 #define VP_FIT2_CHAIN_PRIO 1
 #endif
 template <int W> using SlotGrp = std::conditional_t<VP_FIT2_CHAIN_PRIO != 0, ChainGrp<W, VP_FIT2_CHAIN_PRIO>, Grp<W>>;
+// One reduction round for the residual norm and the Jacobian's Gram values ("Gram round").  An accepted
+// evaluation ran six packed all-reduce rounds in strict sequence; the fourth (||r||^2, one value) and the fifth (the Gram round of
+// jac_qrfac_scaled: Q (Q + 1) / 2 + Q values) read the same registers -- Q^T D_k and Q^T y, final when the last reflector is applied
+// -- and were apart only because the accept decision sits between them.  On: evaluate_core_const_first<..., GQ> forms all partial sums
+// behind house_qr and reduces them in ONE round (3, 6, 10 values for one, two, three exponentials); jac_qrfac_scaled<..., GIN> takes
+// the Gram values from the caller.  A rejected or non-finite evaluation (15 % at the headline) has formed Q (Q + 3) / 2 dot products
+// for nothing.  The same fma chains behind the same masks, and the packed all-reduce gives a value the same tree wherever it sits:
+// bit-identical (tests/test_gpu_gram_round.py against fit_kernel, which keeps the two rounds).  W == 1 sets only (slot loop and lone
+// tail): the LDS exchange of a multi-wave group is bounded by VP_XV.  Each value measured alone against the parent's sources, five
+// alternating rounds, two batches in flight (profiles/gram_round_ab_inflight.json; parent 1.9384-1.9450 ms, spread 0.0066, so a
+// change counts from a margin of 0.020 between its slowest round and the parent's fastest):
+//   0       the two rounds (the code before the switch, instruction for instruction)
+//   1       one round, solve_coeffs behind it (the round needs nothing from the solve; ||e||^2 is added to the reduced sum as
+//           before): 1.9248-1.9284 ms, -0.8 %, margin 0.010 -- every round under the parent's fastest, but NOT by the rule
+//   2 (on)  as 1, with the linear solve branch-free in the round's basic block (solve_coeffs_fast) and its one branch -- to
+//           truncated_solve -- behind the round, so that the solve chain and the reduction overlap: 1.9102-1.9139 ms, -1.5 %,
+//           margin 0.0245; one batch at a time 2.4085-2.4267 against 2.4467-2.4748
+// A set whose slot kernel would spill more VGPRs with the round than without keeps the two rounds: fit2_gram_round() below.
+#ifndef VP_FIT2_GRAM_ROUND
+#define VP_FIT2_GRAM_ROUND 2
+#endif
 #if VP_FIT2_LOCAL_CALLS
 #define VP_SLOT_FN static __noinline__
 #else
@@ -190,6 +211,17 @@ template <typename T, class M, int R, int W, int PADM, int GS, int NG, int WPS> 
 // queue, the persistent grid): the kernels keep their names, and the launcher issues NG / fit2_groups() times the workgroups
 template <typename T, class M, int R, int W, int PADM, int GS, int NG, int WPS> constexpr int fit2_groups() {
     return (VP_FIT2_WAVE_WG == 1 && fit2_global_grid<T, M, R, W, PADM, GS, NG, WPS>()) ? 1 : NG;
+}
+
+// VP_FIT2_GRAM_ROUND per set (the value evaluate_core_const_first's GQ gets; the lone tail follows its kernel): W == 1, and not a
+// set listed here -- one whose slot kernel spills more VGPRs with the round than without (decided at compile time, as fit2_groups
+// does for the general-length variant)
+//   * value 2: the triple exponential + offset in fp64 at 20 rows per lane, full-length variant (6 spilled VGPRs against 2) and
+//     general-length variant (32 against 31)
+// At value 1 no kernel of the library spills more than without the round.
+template <typename T, class M, int R, int W, int PADM> constexpr int fit2_gram_round() {
+    constexpr bool more_spills = VP_FIT2_GRAM_ROUND == 2 && sizeof(T) == 8 && M::N == 4 && M::Q == 3 && R == 20 && PADM != 2;
+    return (W == 1 && M::kDiagonalPairs && M::P == M::Q && !more_spills) ? VP_FIT2_GRAM_ROUND : 0;
 }
 
 // Fill a slot: y' = H_0 y_w into the slot's LDS column (row order, zero padded); returns (H_0 y_w)[0].
@@ -651,7 +683,10 @@ __device__ VP_LONE_TAIL_LINKAGE void fit2_lone_tail(VP_LDS SlotRec<T, M::N, M::Q
     h0.u = h0_u;
     h0.g = h0_g;
     h0.live = true;
-    const T ftol = kc->ftol, xtol = kc->xtol, gtol = kc->gtol, stepbound = kc->stepbound;
+    constexpr int GQ = fit2_gram_round<T, M, R, 1, PADM>();
+    // (GQ: gtol and stepbound -- one use each per accepted step -- are read from the constants where they are used: held across the
+    // sweep they were the one 16-byte spill the Gram round's register allocation left in this function)
+    const T ftol = kc->ftol, xtol = kc->xtol, gtol0 = GQ != 0 ? T(0) : kc->gtol, stepbound0 = GQ != 0 ? T(0) : kc->stepbound;
     const int scale_diag = uni(kc->scale_diag), max_fev = uni(kc->max_fev), mres = uni(kc->m);
     const int64_t prob = uni(rec->prob);
     const T qty0 = rec->qty0;
@@ -744,7 +779,10 @@ __device__ VP_LONE_TAIL_LINKAGE void fit2_lone_tail(VP_LDS SlotRec<T, M::N, M::Q
         T C[NC][R];
         EvalUniform<T, N> u;
         load_rows_lds<T, R, 1>((const T *)s_col, lane, C[YC]);
-        evaluate_core_const_first<T, M, R, NC, Src, G, true>(mdl, xt, src, eps, grp, h0, C, u, nullptr, qty0);
+        T gq[Q * (Q + 1) / 2 + Q]; // (GQ) the Jacobian's Gram values, reduced with ||r||^2
+        (void)gq;
+        if constexpr (GQ != 0) evaluate_core_const_first<T, M, R, NC, Src, G, true, false, false, false, GQ>(mdl, xt, src, eps, grp, h0, C, u, nullptr, qty0, nullptr, nullptr, gq);
+        else evaluate_core_const_first<T, M, R, NC, Src, G, true>(mdl, xt, src, eps, grp, h0, C, u, nullptr, qty0);
         asm volatile("" ::: "memory");
         chain_raise_scalar(grp); // (the inline, wave-uniform bookkeeping: one dependent chain up to the next sweep)
         unpark();
@@ -844,7 +882,8 @@ __device__ VP_LONE_TAIL_LINKAGE void fit2_lone_tail(VP_LDS SlotRec<T, M::N, M::Q
             T zs[Q];
 #pragma unroll
             for (int k = 0; k < Q; ++k) zs[k] = -u.c[k];
-            jac_qrfac_scaled<T, R, Q, N>(reinterpret_cast<T(&)[Q][R]>(C[DC]), C[YC], zs, Rj, acnorm, ipvt, qtf, grp);
+            if constexpr (GQ != 0) jac_qrfac_scaled<T, R, Q, N, G, true>(reinterpret_cast<T(&)[Q][R]>(C[DC]), C[YC], zs, Rj, acnorm, ipvt, qtf, grp, gq);
+            else jac_qrfac_scaled<T, R, Q, N>(reinterpret_cast<T(&)[Q][R]>(C[DC]), C[YC], zs, Rj, acnorm, ipvt, qtf, grp);
             chain_raise_scalar(grp);
             if (uni(jac_not_finite<T, Q>(acnorm))) { // (rare) flag and re-fit: vp_fit.hpp, jac_not_finite
                 term = VP_TERM_NUMERICAL;
@@ -871,6 +910,7 @@ __device__ VP_LONE_TAIL_LINKAGE void fit2_lone_tail(VP_LDS SlotRec<T, M::N, M::Q
                 term = VP_TERM_NUMERICAL;
                 break;
             }
+            const T gtol = GQ != 0 ? kc->gtol : gtol0;
             if (uni(gnorm <= gtol)) {
                 term = VP_TERM_ORTHOGONAL;
                 break;
@@ -887,6 +927,7 @@ __device__ VP_LONE_TAIL_LINKAGE void fit2_lone_tail(VP_LDS SlotRec<T, M::N, M::Q
                     term = VP_TERM_NUMERICAL;
                     break;
                 }
+                const T stepbound = GQ != 0 ? kc->stepbound : stepbound0;
                 delta = (xnorm == T(0)) ? stepbound : stepbound * xnorm;
                 first_update = false;
             } else if (scale_diag) {
@@ -1150,8 +1191,12 @@ fit2_kernel(const Fit2Args<T, M> args) {
             T C[NC][R];
             EvalUniform<T, N> u;
             load_rows_lds<T, R, W>(s_y + (size_t)s * MP, W == 1 ? lane_fresh() : lane, C[YC]);
-            evaluate_core_const_first<T, M, R, NC, Src, G, true, false, false, kPre>(mdl, alpha, src, eps_, grp, h0, C, u, nullptr, qty0, nullptr,
-                                                                                      rec->pre); // (read from LDS where they are used)
+            constexpr int GQ = fit2_gram_round<T, M, R, W, PADM>();
+            T gq[Q * (Q + 1) / 2 + Q]; // (GQ) the Jacobian's Gram values, reduced with ||r||^2
+            (void)gq;
+            evaluate_core_const_first<T, M, R, NC, Src, G, true, false, false, kPre, GQ>(mdl, alpha, src, eps_, grp, h0, C, u, nullptr, qty0, nullptr,
+                                                                                          rec->pre, // (read from LDS where they are used)
+                                                                                          GQ != 0 ? gq : nullptr);
 
             chain_raise_scalar(grp); // (wave-uniform from here to the next slot's sweep, but for the Jacobian's row loops)
             const T fnorm1 = usqrt(u.fn2);
@@ -1173,7 +1218,8 @@ fit2_kernel(const Fit2Args<T, M> args) {
                 T zs[Q];
 #pragma unroll
                 for (int k = 0; k < Q; ++k) zs[k] = -u.c[k];
-                jac_qrfac_scaled<T, R, Q, N>(reinterpret_cast<T(&)[Q][R]>(C[DC]), C[YC], zs, Rj, acnorm, ipvt, qtf, grp);
+                if constexpr (GQ != 0) jac_qrfac_scaled<T, R, Q, N, G, true>(reinterpret_cast<T(&)[Q][R]>(C[DC]), C[YC], zs, Rj, acnorm, ipvt, qtf, grp, gq);
+                else jac_qrfac_scaled<T, R, Q, N>(reinterpret_cast<T(&)[Q][R]>(C[DC]), C[YC], zs, Rj, acnorm, ipvt, qtf, grp);
                 chain_raise_scalar(grp);
             }
             if (lane == 0) { // group lane 0
