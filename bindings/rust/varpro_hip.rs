@@ -57,6 +57,12 @@ pub const VP_BASIS_EXP_DECAY_IRF: i32 = 9;
 pub const VP_BASIS_IRF: i32 = 10;
 /// the periodic form of kind 9: the response repeats every period `T >= m dt` (`vp_set_irf_period`; default `T = m dt`)
 pub const VP_BASIS_EXP_DECAY_IRF_PERIODIC: i32 = 11;
+/// kind 9 on the response shifted by `p1 = delta` (grid units, positive: later; cubic interpolation, zero outside the record)
+pub const VP_BASIS_EXP_DECAY_IRF_SHIFT: i32 = 12;
+/// the shifted response itself, `p0 = delta`; all shifted functions of a descriptor name the same delta
+pub const VP_BASIS_IRF_SHIFT: i32 = 13;
+/// kind 11 on the shifted response, `p1 = delta`
+pub const VP_BASIS_EXP_DECAY_IRF_PERIODIC_SHIFT: i32 = 14;
 pub const VP_F64: i32 = 0;
 pub const VP_FLAG_OWN_STREAM: i32 = 8;
 pub const VP_FLAG_NO_GRID_RECURRENCE: i32 = 16;

@@ -80,7 +80,13 @@ enum {
     VP_BASIS_IRF = 10,          /* irf_i                   invariant (no parameters): the scattered-light term             */
     /* kind 9 with the response repeating every period T = P dt, P >= m real (see "Periodic IRF reconvolution" below):
      * sum_{p>=0} sum_k irf_k rho^(i-k+pP) over the terms with i-k+pP >= 0; the same recurrence from a non-zero start   */
-    VP_BASIS_EXP_DECAY_IRF_PERIODIC = 11
+    VP_BASIS_EXP_DECAY_IRF_PERIODIC = 11,
+    /* kinds 9 - 11 on the response SHIFTED by delta, a fit parameter (see "Shifted IRF reconvolution" below): g_i = r(i - s),
+     * s = delta/dt, r the Catmull-Rom cubic through the samples, zero outside the record; g' = dg/ddelta                  */
+    VP_BASIS_EXP_DECAY_IRF_SHIFT = 12, /* p0 = tau, p1 = delta: kind 9 on g; d/dp0 as kind 9, d/dp1 = kind 9's Phi on g'   */
+    VP_BASIS_IRF_SHIFT = 13,           /* p0 = delta: g_i; d/dp0 = g'_i   (the scattered-light term, shifted)              */
+    VP_BASIS_EXP_DECAY_IRF_PERIODIC_SHIFT = 14 /* p0 = tau, p1 = delta: kind 11 on g (the period of vp_set_irf_period);
+                                                  d/dp1 = kind 11's Phi on g'                                              */
 };
 
 /*
@@ -152,6 +158,39 @@ enum {
  * period < m dt_b (1 - 1e-6) on any grid is VP_ERR_INVALID; within that band g is taken as 0.  Device-pointer grids are the
  * caller's contract: g < -1e-6 m gives NaN columns, latched per problem like tau <= 0.  A descriptor with this kind needs
  * m >= 2 (m = 1: dt = 0, the periodic sum diverges) -- creation answers VP_ERR_INVALID -- and may mix kinds 9, 10 and 11.
+ *
+ * Shifted IRF reconvolution.  A measured response is recorded at another wavelength or count rate than the decay and sits a
+ * fraction of a bin to a few bins away from where the decay's rising edge wants it.  The kinds 12 - 14 are the kinds 9 - 11
+ * on the response shifted by delta, a nonlinear parameter like any other (bounds, fixing, vp_search, the statistics).  The
+ * grid is uniform with step dt as for kind 9; delta is in the units of the grid, s = delta/dt in bins, and a POSITIVE delta
+ * moves the response to LATER times.  The response is ZERO OUTSIDE THE RECORD: nothing wraps, not for the periodic kind
+ * either -- this suits responses that are negligible at the record's edges.  g_i = r(i - s), with r the Catmull-Rom cubic
+ * through the samples:
+ *     o = floor(-s),  f = -s - o  in [0,1)                                   (both uniform over the problem)
+ *     g_i              =         sum_{a=-1..2} w_a(f)  irf_{i+o+a}
+ *     dg_i/ddelta = g'_i = -(1/dt) sum_{a=-1..2} w'_a(f) irf_{i+o+a}
+ *     w_-1  = (-f^3+2f^2-f)/2    w_0  = (3f^3-5f^2+2)/2    w_1  = (-3f^3+4f^2+f)/2    w_2  = (f^3-f^2)/2
+ *     w'_-1 = (-3f^2+4f-1)/2     w'_0 = (9f^2-10f)/2       w'_1 = (-9f^2+8f+1)/2      w'_2 = (3f^2-2f)/2
+ * (sum w = 1, sum w' = 0; g' is continuous across integer shifts, so the Jacobian has no jumps -- which is why the
+ * interpolant is cubic and not linear; f = 0 gives w = (0, 1, 0, 0) exactly: delta = 0 reproduces the response bit for bit,
+ * an integer shift moves its samples exactly, zeros shifted in).  Because the recurrences of kinds 9 and 11, and the
+ * steady-state carry of kind 11, are linear in the response, every column of a shifted kind is an existing scan over g or g':
+ *     12 (tau, delta):  Phi, d/dtau = kind 9 on g;   d/ddelta = the Phi recurrence of kind 9 on g'
+ *     13 (delta):       Phi = g;                     d/ddelta = g'
+ *     14 (tau, delta):  Phi, d/dtau = kind 11 on g;  d/ddelta = kind 11's Phi on g'
+ * One resample kernel (vp_irf_shift.hpp) writes g and g' per problem into two buffers the handle owns -- [B][ms] each, ms = m
+ * rounded up to a 16-byte group, 2 B ms elements of the handle's dtype, allocated at the first call that needs columns -- and
+ * the scan kernels of kinds 9 - 11 run over them, unchanged.  Under vp_set_bounds delta = g(u) like every parameter (g' is
+ * multiplied by ddelta/du in the resample kernel); on a vp_batch_create_fixed handle a fixed delta is read per problem from
+ * the fixed values and has no derivative column.  Rules:
+ *   - all functions of kinds 12 - 14 of one descriptor name the SAME delta parameter (one response, one shift), and no
+ *     function of another kind -- nor the tau of a shifted function -- may be that parameter: else VP_ERR_INVALID at creation;
+ *   - m >= 2 (dt = 0 otherwise): VP_ERR_INVALID at creation, as for kind 11;
+ *   - a non-finite s gives NaN columns, latched per problem like tau <= 0; |s| >= m + 2 gives exact zeros in g and g';
+ *   - kinds 9 - 11 may stand next to 12 - 14 in one descriptor: they keep reading the handle's own, unshifted response;
+ *   - vp_set_irf, vp_set_irf_period (kind 14 counts as periodic), vp_basis into caller arrays, S > 1, both dtypes, grids
+ *     and responses per problem work as for kinds 9 - 11; vp_search on such a handle takes its candidate loop (as for a
+ *     response per problem), because g belongs to the problem, not to the candidate.
  *
  * Parameters for which Phi is not finite (a NaN guess; p1 = 0 with p0 on a grid point: 0 / 0) are latched per problem in
  * status[b], like a caller's non-finite columns; p1 = 0 elsewhere gives a finite Phi (exp(-inf) = 0) whose Gaussian

@@ -31,6 +31,7 @@ VP_ROBUST_HUBER, VP_ROBUST_CAUCHY, VP_ROBUST_TUKEY = 0, 1, 2
 VP_BASIS_CONST, VP_BASIS_EXP_DECAY, VP_BASIS_EXP_RATE, VP_BASIS_EXP_COS, VP_BASIS_SIN_PHASE, VP_BASIS_EXTERNAL = 0, 1, 2, 3, 4, 5
 VP_BASIS_GAUSS, VP_BASIS_LORENTZ, VP_BASIS_LINEAR = 6, 7, 8
 VP_BASIS_EXP_DECAY_IRF, VP_BASIS_IRF, VP_BASIS_EXP_DECAY_IRF_PERIODIC = 9, 10, 11
+VP_BASIS_EXP_DECAY_IRF_SHIFT, VP_BASIS_IRF_SHIFT, VP_BASIS_EXP_DECAY_IRF_PERIODIC_SHIFT = 12, 13, 14
 VP_FIT_DERIVATIVES_ON_ACCEPT = 1
 VP_WANT_BASIS, VP_WANT_DERIVATIVES = 1, 2
 VP_KERNEL_EVALUATE, VP_KERNEL_BASIS, VP_KERNEL_FIT = 0, 1, 2

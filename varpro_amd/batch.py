@@ -243,7 +243,7 @@ class BatchProblem:
         self._grid_step = None
         if self.irf_kinds and not self.device_mode:
             self._grid_step = _uniform_step(x)  # (a device grid is the caller's contract: include/varpro_hip.h)
-        self.irf_periodic = (not self.external) and _basis.EXP_DECAY_IRF_PERIODIC in model.kinds
+        self.irf_periodic = (not self.external) and any(k in _basis.PERIODIC_KINDS for k in model.kinds)
         if irf_period is not None:
             irf_period = self._checked_irf_period(irf_period)
         self._keep = (x, Y, w)

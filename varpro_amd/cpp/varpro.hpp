@@ -45,7 +45,12 @@ enum class Basis : int32_t {
     ExpDecayIrf = VP_BASIS_EXP_DECAY_IRF,
     Irf = VP_BASIS_IRF,
     // ... with the response repeating every period T >= m dt (BatchProblem::set_irf_period; default: the record is one period)
-    ExpDecayIrfPeriodic = VP_BASIS_EXP_DECAY_IRF_PERIODIC
+    ExpDecayIrfPeriodic = VP_BASIS_EXP_DECAY_IRF_PERIODIC,
+    // ... on the response shifted by delta, the function's last parameter (grid units, positive: later; cubic interpolation,
+    // zero outside the record).  All shifted functions of a model name the same delta; the library checks it at creation
+    ExpDecayIrfShift = VP_BASIS_EXP_DECAY_IRF_SHIFT,                  // (tau, delta)
+    IrfShift = VP_BASIS_IRF_SHIFT,                                    // (delta)
+    ExpDecayIrfPeriodicShift = VP_BASIS_EXP_DECAY_IRF_PERIODIC_SHIFT  // (tau, delta)
 };
 inline int arity(Basis k) {
     switch (k) {
@@ -55,6 +60,7 @@ inline int arity(Basis k) {
     case Basis::ExpDecay:
     case Basis::ExpRate:
     case Basis::ExpDecayIrf:
+    case Basis::IrfShift:
     case Basis::ExpDecayIrfPeriodic: return 1;
     default: return 2;
     }

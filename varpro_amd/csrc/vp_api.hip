@@ -354,6 +354,10 @@ struct __attribute__((visibility("hidden"))) vp_batch {
     // the longest record m dt_b of the batch (< 0: a device grid, the caller's contract)
     bool irf_periodic = false;
     double irf_period = 0.0, irf_span_max = -1.0;
+    // shifted IRF kinds (vp_irf_shift.hpp): the shifted response g and dg/ddelta of every problem, written by the resample
+    // kernel in front of the scans; [B][irf_gs] each, irf_gs = rows rounded up to a 16-byte group; allocated at first use
+    bool irf_shift = false;
+    void *d_irf_g = nullptr, *d_irf_dg = nullptr;
     // fixed nonlinear parameters (vp_batch_create_fixed): the handle is the REDUCED model -- q, p, the pair table and d_alpha
     // are those of the free parameters in model order; col_model stays the full descriptor and only the column kernels'
     // fixed siblings (vp_cols.hpp, vp_irf.hpp) read the map and the values
@@ -657,6 +661,17 @@ int ensure_R(vp_batch *h) { return h->ensure(h->d_R, (size_t)h->B * h->S * h->m 
 // ---- device-column handles: the column kernel (vp_cols.hpp) ------------------------------------------------------------
 // rows of a column: the caller's m (a handle padded for m < n keeps the caller's rows in its columns, like ext_rows)
 int64_t col_rows(const vp_batch *h) { return h->m_user ? h->m_user : h->m; }
+// shifted IRF kinds: the row stride of the handle's g / g' buffers (whole 16-byte groups), and the buffers themselves
+int64_t irf_shift_stride(const vp_batch *h) {
+    const int64_t vw = (int64_t)(16 / tsize(h->dtype));
+    return (col_rows(h) + vw - 1) / vw * vw;
+}
+int ensure_irf_shift(vp_batch *h) {
+    if (!h->irf_shift) return 0;
+    const size_t bytes = (size_t)h->B * (size_t)irf_shift_stride(h) * tsize(h->dtype);
+    if (int rc = h->ensure(h->d_irf_g, bytes)) return rc;
+    return h->ensure(h->d_irf_dg, bytes);
+}
 // the launch record of the handle's model on the handle's grid; outputs and the problem selection are the caller's
 void fill_cols_params(const vp_batch *h, ColsParams &c) {
     std::memset(&c, 0, sizeof(c));
@@ -669,6 +684,9 @@ void fill_cols_params(const vp_batch *h, ColsParams &c) {
     c.irf = h->d_irf;
     c.irf_stride = h->irf_stride;
     c.irf_period = h->irf_period;
+    c.irf_g = h->d_irf_g;
+    c.irf_dg = h->d_irf_dg;
+    c.irf_gs = irf_shift_stride(h);
     c.stream = h->stream;
     if (h->fixed) { // the fixed siblings: alpha over the free parameters, an infinite box unless the caller sets the fit's
         c.fix_src = h->fix_src;
@@ -697,6 +715,7 @@ int fill_own_columns(vp_batch *h, const void *alpha_dev, const int32_t *list, co
     if (int rc = h->ensure(h->col_phi, (size_t)h->B * h->n * rows * ts)) return rc;
     if (h->ext_np > 0)
         if (int rc = h->ensure(h->col_dphi, (size_t)h->B * h->ext_np * rows * ts)) return rc;
+    if (int rc = ensure_irf_shift(h)) return rc;
     ColsParams c;
     fill_cols_params(h, c);
     c.alpha = alpha_dev;
@@ -1240,6 +1259,23 @@ static int batch_create(vp_batch **out, const vp_model_desc *model, int dtype, i
             if (model->kind[j] == VP_BASIS_EXP_DECAY_IRF_PERIODIC)
                 return fail(VP_ERR_INVALID, "VP_BASIS_EXP_DECAY_IRF_PERIODIC needs m >= 2: one sample has dt = 0, the periodic sum "
                                             "diverges");
+            else if (is_irf_shift_kind(model->kind[j]))
+                return fail(VP_ERR_INVALID, "the shifted IRF kinds (VP_BASIS_EXP_DECAY_IRF_SHIFT / VP_BASIS_IRF_SHIFT / "
+                                            "VP_BASIS_EXP_DECAY_IRF_PERIODIC_SHIFT) need m >= 2: one sample has dt = 0, the shift "
+                                            "in bins is undefined");
+    // one response, one shift: every function of a shifted kind names the same delta, nothing else depends on it
+    if (model && !ext && model->n_basis > 0 && model->n_basis <= VP_MAX_BASIS) {
+        const int delta = irf_shift_param(*model);
+        for (int j = 0; delta >= 0 && j < model->n_basis; ++j) {
+            const int kind = model->kind[j];
+            const int own = !is_irf_shift_kind(kind) ? -1 : (kind == VP_BASIS_IRF_SHIFT ? 0 : 1); // the argument that is delta
+            for (int k = 0; k < VP_MAX_BASIS_PARAMS; ++k)
+                if (k == own ? model->param[j][k] != delta : model->param[j][k] == delta)
+                    return fail(VP_ERR_INVALID, "the shifted IRF kinds: all functions of VP_BASIS_EXP_DECAY_IRF_SHIFT / VP_BASIS_IRF_SHIFT "
+                                                "/ VP_BASIS_EXP_DECAY_IRF_PERIODIC_SHIFT must name the same shift parameter, and no "
+                                                "other function or argument may be that parameter");
+        }
+    }
     // the IRF reconvolution kinds need a uniform grid; a host grid is checked here (a device grid is the caller's contract)
     if (model && !ext && t && !dev_data && m > 0 && B > 0 && (dtype == VP_F64 || dtype == VP_F32) && model->n_basis > 0 &&
         model->n_basis <= VP_MAX_BASIS) {
@@ -1633,7 +1669,9 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
         for (int j = 0; j < descriptor->n_basis; ++j)
             if (is_irf_kind(descriptor->kind[j])) h->irf_kinds = true;
         for (int j = 0; j < descriptor->n_basis; ++j)
-            if (descriptor->kind[j] == VP_BASIS_EXP_DECAY_IRF_PERIODIC) h->irf_periodic = true;
+            if (descriptor->kind[j] == VP_BASIS_EXP_DECAY_IRF_PERIODIC || descriptor->kind[j] == VP_BASIS_EXP_DECAY_IRF_PERIODIC_SHIFT)
+                h->irf_periodic = true;
+        h->irf_shift = irf_shift_param(*descriptor) >= 0;
         if (fix) {
             h->fixed = true;
             h->q_full = descriptor->n_params;
@@ -2009,6 +2047,7 @@ int vp_basis(vp_batch *h, const void *alpha, void *Phi_out, void *dPhi_out, int 
         OutBuf phi, dphi;
         if (int rc = phi.init(h, Phi_out, (size_t)h->B * nc * rows * ts)) return rc;
         if (int rc = dphi.init(h, dPhi_out, (size_t)h->B * h->ext_np * rows * ts)) return rc;
+        if (int rc = ensure_irf_shift(h)) return rc;
         ColsParams c;
         fill_cols_params(h, c);
         c.alpha = a.dptr;
@@ -2426,6 +2465,7 @@ int vp_search(vp_batch *h, const void *cand, int64_t K, int flags, void *alpha_o
     h->r_valid = false;
     const bool shared = !per_problem && !(h->flags & (VP_FLAG_T_PER_PROBLEM | VP_FLAG_W_PER_PROBLEM)) && !h->m_user &&
                         !(h->irf_kinds && h->irf_stride != 0) && // (a response per problem: the candidate loop, like a grid per problem)
+                        !h->irf_shift &&                         // (a shifted kind: g belongs to the problem, not to the candidate)
                         !(h->fixed && h->fix_stride != 0);       // (fixed values per problem: the same)
     {
         SearchClock clk(h);
@@ -3041,6 +3081,9 @@ static int kind_arity(int kind) {
     case VP_BASIS_EXP_DECAY_IRF: return 1;
     case VP_BASIS_IRF: return 0;
     case VP_BASIS_EXP_DECAY_IRF_PERIODIC: return 1;
+    case VP_BASIS_EXP_DECAY_IRF_SHIFT: return 2;
+    case VP_BASIS_IRF_SHIFT: return 1;
+    case VP_BASIS_EXP_DECAY_IRF_PERIODIC_SHIFT: return 2;
     default: return -1; // (VP_BASIS_EXTERNAL never reaches a descriptor: vp_batch_create_external only)
     }
 }

@@ -60,6 +60,9 @@ struct ColsParams {
     const void *irf;       // descriptors with an IRF kind: the response, [m] or [B][irf_stride] (vp_irf.hpp)
     int64_t irf_stride;    // 0: one response for all problems
     double irf_period;     // VP_BASIS_EXP_DECAY_IRF_PERIODIC: the period in grid units, 0: the record is one period
+    // descriptors with a shifted IRF kind (vp_irf_shift.hpp): the handle's buffers for the shifted response and its derivative
+    void *irf_g, *irf_dg;  // [B][irf_gs] each, 16-byte aligned, indexed by the problem
+    int64_t irf_gs;        // m rounded up to a 16-byte group
     hipStream_t stream;
     // fixed parameters (vp_batch_create_fixed): `model` is the FULL descriptor, `alpha` (and lo / hi, which this form always
     // needs: an infinite box where the fit has none) is [B][q_free] over the free parameters in model order
@@ -74,8 +77,20 @@ int irf_cols_fill(const ColsParams &p); // the columns of the IRF kinds alone (v
 // the same two for a record with fix_src (the fixed siblings: vp_inst_cols_fixed.hip)
 int cols_fill_fixed(const ColsParams &p);
 int irf_cols_fill_fixed(const ColsParams &p);
+// g and g' of the shifted IRF kinds into p.irf_g / p.irf_dg (vp_inst_irf_shift.hip); delta_param: delta's index among the
+// descriptor's parameters; want_dg: g' as well (never written for a delta that p.fix_src fixes)
+int irf_resample(const ColsParams &p, int delta_param, bool want_dg);
+inline bool is_irf_shift_kind(const int kind) {
+    return kind == VP_BASIS_EXP_DECAY_IRF_SHIFT || kind == VP_BASIS_IRF_SHIFT || kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC_SHIFT;
+}
 inline bool is_irf_kind(const int kind) {
-    return kind == VP_BASIS_EXP_DECAY_IRF || kind == VP_BASIS_IRF || kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC;
+    return kind == VP_BASIS_EXP_DECAY_IRF || kind == VP_BASIS_IRF || kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC || is_irf_shift_kind(kind);
+}
+// the shift parameter of a descriptor: delta's index, -1 without a shifted kind (creation checks that there is only one)
+inline int irf_shift_param(const vp_model_desc &model) {
+    for (int j = 0; j < model.n_basis && j < VP_MAX_BASIS; ++j)
+        if (is_irf_shift_kind(model.kind[j])) return model.param[j][model.kind[j] == VP_BASIS_IRF_SHIFT ? 0 : 1];
+    return -1;
 }
 // the column numbering of a descriptor: phi_col[j] the Phi column of function j (-1: skipped, a VP_BASIS_CONST under
 // skip_invariant), first_pair[j] its first derivative column in dPhi (pairs in model order), and the totals.  fix_src
@@ -480,6 +495,7 @@ template <typename T, bool FIX = false> int launch_fill(const ColsParams &p) {
     // VP_BASIS_IRF simply (it has no parameters), and at every VP_BASIS_EXP_DECAY_IRF[_PERIODIC] the descriptor is cut, the run of
     // functions behind it going to a launch of its own whose dPhi starts at that run's first pair.  A descriptor without
     // these kinds is one run: the launch it always was.  (FIX: first_pair counts the FREE pairs in front of the run.)
+    // The shifted kinds cut the descriptor as well -- VP_BASIS_IRF_SHIFT too: unlike VP_BASIS_IRF it HAS a pair.
     a.mdl = p.model;
     int run = 0, run_pair0 = 0;
     bool stores = false; // the run has a column to write
@@ -497,7 +513,7 @@ template <typename T, bool FIX = false> int launch_fill(const ColsParams &p) {
     for (int j = 0; j < p.model.n_basis; ++j) {
         const int kind = p.model.kind[j];
         if (kind == VP_BASIS_IRF) continue;
-        if (kind == VP_BASIS_EXP_DECAY_IRF || kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC) {
+        if (kind == VP_BASIS_EXP_DECAY_IRF || kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC || is_irf_shift_kind(kind)) {
             if (int rc = flush()) return rc;
             continue;
         }

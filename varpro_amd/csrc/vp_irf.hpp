@@ -40,6 +40,10 @@
 // row -- the zero padding of the last tile never enters the totals -- one v_readlane pair delivers (A, B), the carry is formed
 // from wave-uniform values, and pass 1 is the scan of kind 9 from that carry.  The response is read twice (the second time
 // from cache), nothing is written twice; no LDS, no barrier.  period == 0: T = m dt_b; T < m dt (1 - 1e-6): NaN columns.
+//
+// The shifted kinds VP_BASIS_EXP_DECAY_IRF_SHIFT / VP_BASIS_IRF_SHIFT / VP_BASIS_EXP_DECAY_IRF_PERIODIC_SHIFT have no kernel
+// here: launch_irf below sends them through these kernels as kinds 9 / 10 / 11 over the shifted response g and over
+// dg/ddelta, which the resample kernel (vp_irf_shift.hpp) writes per problem first.
 #pragma once
 #include <type_traits>
 
@@ -259,12 +263,18 @@ __global__ void __launch_bounds__(256) irf_cols_periodic_fixed_kernel(const IrfF
 // the columns of the IRF kinds: one launch of irf_cols_kernel over the functions of kinds 9 and 10, one of
 // irf_cols_periodic_kernel over those of kind 11 (a descriptor may mix them; the pairs are numbered over the whole descriptor)
 // FIX: the record has fix_src -- the fixed siblings alone (their instantiations live in a unit of their own)
+//
+// The shifted kinds 12 / 13 / 14 (vp_irf_shift.hpp) go to the SAME kernels as kinds 9 / 10 / 11, in passes of their own behind
+// the resample kernel: a value pass over g (Phi and d/dtau where the unshifted kinds read the handle's response), and, where
+// dPhi is wanted and delta is free, a derivative pass over g' in which the kernel's "Phi" is the dPhi array and a function's
+// "Phi column" the pair (function, delta) -- the kernel's own derivative output is dropped (a.dphi = nullptr).
 template <typename T, bool FIX = false> int launch_irf(const ColsParams &p) {
     if (p.B <= 0 || p.m <= 0 || (!p.phi && !p.dphi)) return VP_ERR_OK;
     if (!p.irf) return VP_ERR_INVALID;
     if (FIX && !(p.fix_src && p.fix_values && p.lo && p.hi)) return VP_ERR_INVALID;
-    const bool vec = vec_groups<T>(p, p.irf, p.irf_stride), bounded = p.lo && p.hi;
+    const bool bounded = p.lo && p.hi;
     const ColumnMap map = column_map(p.model, p.skip_invariant, FIX ? p.fix_src : nullptr);
+    auto is_free = [&](const int k) { return k >= 0 && !(FIX && p.fix_src[k] < 0); }; // the parameter has a derivative column
     std::conditional_t<FIX, IrfFixedArgs<T>, IrfArgs<T>> a;
     if constexpr (FIX) {
         a.values = (const T *)p.fix_values;
@@ -272,67 +282,96 @@ template <typename T, bool FIX = false> int launch_irf(const ColsParams &p) {
     }
     a.t = (const T *)p.t;
     a.alpha = (const T *)p.alpha;
-    a.irf = (const T *)p.irf;
-    a.phi = (T *)p.phi;
-    a.dphi = map.n_pairs > 0 ? (T *)p.dphi : nullptr;
     a.lo = (const T *)p.lo;
     a.hi = (const T *)p.hi;
     a.list = p.list;
     a.count = p.count;
     a.t_stride = p.t_stride;
-    a.irf_stride = p.irf_stride;
     a.bound_stride = p.bound_stride;
     a.m = p.m;
     a.q = FIX ? p.q_free : p.model.n_params;
-    a.n_phi_cols = map.n_phi_cols;
     a.n_pairs = map.n_pairs;
     const T period = (T)p.irf_period;
-    for (int periodic = 0; periodic < 2; ++periodic) {
-        int nf = 0;
-        for (int j = 0; j < p.model.n_basis && j < VP_MAX_BASIS; ++j) {
-            const int kind = p.model.kind[j];
-            const bool wanted = periodic ? kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC
-                                         : (kind == VP_BASIS_IRF ? p.phi != nullptr : kind == VP_BASIS_EXP_DECAY_IRF);
-            if (!wanted) continue;
-            a.kind[nf] = kind;
-            a.phi_col[nf] = map.phi_col[j];
-            a.pair[nf] = map.first_pair[j];
-            a.param[nf] = p.model.param[j][0];
-            if constexpr (FIX) { // (a VP_BASIS_IRF has no parameter: nothing is read for it)
-                const int k = p.model.param[j][0];
-                a.fixed_param[nf] = k >= 0 && p.fix_src[k] < 0 ? k : -1;
-                a.param[nf] = k >= 0 && p.fix_src[k] >= 0 ? p.fix_src[k] : 0;
-            }
-            ++nf;
+    enum { UNSHIFTED = 0, SHIFT_VALUE = 1, SHIFT_DELTA = 2 };
+    // one pass over the response `src`: the functions of the unshifted kinds, or those of the shifted kinds as kinds 9 - 11
+    auto run = [&](const int pass, const void *src, const int64_t src_stride) -> int {
+        const bool vec = vec_groups<T>(p, src, src_stride);
+        a.irf = (const T *)src;
+        a.irf_stride = src_stride;
+        if (pass == SHIFT_DELTA) {
+            a.phi = (T *)p.dphi;
+            a.n_phi_cols = map.n_pairs;
+            a.dphi = nullptr;
+        } else {
+            a.phi = (T *)p.phi;
+            a.n_phi_cols = map.n_phi_cols;
+            a.dphi = map.n_pairs > 0 ? (T *)p.dphi : nullptr;
         }
-        if (nf == 0) continue;
-        for (int f = nf; f < VP_MAX_BASIS; ++f) a.kind[f] = a.phi_col[f] = a.pair[f] = a.param[f] = 0;
-        if constexpr (FIX)
-            for (int f = nf; f < VP_MAX_BASIS; ++f) a.fixed_param[f] = -1;
-        a.nf = nf;
-        // (4 waves per workgroup)
-        const int rc = launch_chunks(p.B, (int64_t)0x7fffffff / nf, [&](const int64_t first, const int64_t nb) {
-            a.first = first;
-            a.slots = nb;
-            const dim3 grid((unsigned)((nb * nf + 3) / 4)), block(256);
-            if constexpr (FIX) {
-                select_variant(
-                    [&](auto V, auto N, auto PER) {
-                        if constexpr (PER.value) hipLaunchKernelGGL((irf_cols_periodic_fixed_kernel<T, V.value, N.value>), grid, block, 0, p.stream, a, period);
-                        else hipLaunchKernelGGL((irf_cols_fixed_kernel<T, V.value, N.value>), grid, block, 0, p.stream, a);
-                    },
-                    vec, p.nt != 0, periodic != 0);
-            } else {
-                select_variant(
-                    [&](auto V, auto N, auto BD, auto PER) {
-                        if constexpr (PER.value) hipLaunchKernelGGL((irf_cols_periodic_kernel<T, V.value, N.value, BD.value>), grid, block, 0, p.stream, a, period);
-                        else hipLaunchKernelGGL((irf_cols_kernel<T, V.value, N.value, BD.value>), grid, block, 0, p.stream, a);
-                    },
-                    vec, p.nt != 0, bounded, periodic != 0);
+        for (int periodic = 0; periodic < 2; ++periodic) {
+            int nf = 0;
+            for (int j = 0; j < p.model.n_basis && j < VP_MAX_BASIS; ++j) {
+                int kind = p.model.kind[j]; // (as the kernel sees it)
+                if (is_irf_shift_kind(kind) != (pass != UNSHIFTED)) continue;
+                if (kind == VP_BASIS_EXP_DECAY_IRF_SHIFT) kind = VP_BASIS_EXP_DECAY_IRF;
+                else if (kind == VP_BASIS_IRF_SHIFT) kind = VP_BASIS_IRF;
+                else if (kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC_SHIFT) kind = VP_BASIS_EXP_DECAY_IRF_PERIODIC;
+                const bool wanted = periodic ? kind == VP_BASIS_EXP_DECAY_IRF_PERIODIC
+                                             : (kind == VP_BASIS_IRF ? a.phi != nullptr : kind == VP_BASIS_EXP_DECAY_IRF);
+                if (!wanted) continue;
+                const int k = kind == VP_BASIS_IRF ? -1 : p.model.param[j][0]; // tau (a VP_BASIS_IRF reads no parameter)
+                a.kind[nf] = kind;
+                a.phi_col[nf] = map.phi_col[j];
+                if (pass == SHIFT_DELTA) { // the pair (j, delta): behind the pair of tau where tau is free
+                    if (!is_free(p.model.param[j][kind == VP_BASIS_IRF ? 0 : 1])) continue;
+                    a.phi_col[nf] = map.first_pair[j] + (is_free(k) ? 1 : 0);
+                }
+                a.pair[nf] = map.first_pair[j];
+                a.param[nf] = k >= 0 ? k : 0;
+                if constexpr (FIX) {
+                    a.fixed_param[nf] = k >= 0 && p.fix_src[k] < 0 ? k : -1;
+                    a.param[nf] = k >= 0 && p.fix_src[k] >= 0 ? p.fix_src[k] : 0;
+                }
+                ++nf;
             }
-        });
-        if (rc) return rc;
-    }
+            if (nf == 0) continue;
+            for (int f = nf; f < VP_MAX_BASIS; ++f) a.kind[f] = a.phi_col[f] = a.pair[f] = a.param[f] = 0;
+            if constexpr (FIX)
+                for (int f = nf; f < VP_MAX_BASIS; ++f) a.fixed_param[f] = -1;
+            a.nf = nf;
+            // (4 waves per workgroup)
+            const int rc = launch_chunks(p.B, (int64_t)0x7fffffff / nf, [&](const int64_t first, const int64_t nb) {
+                a.first = first;
+                a.slots = nb;
+                const dim3 grid((unsigned)((nb * nf + 3) / 4)), block(256);
+                if constexpr (FIX) {
+                    select_variant(
+                        [&](auto V, auto N, auto PER) {
+                            if constexpr (PER.value) hipLaunchKernelGGL((irf_cols_periodic_fixed_kernel<T, V.value, N.value>), grid, block, 0, p.stream, a, period);
+                            else hipLaunchKernelGGL((irf_cols_fixed_kernel<T, V.value, N.value>), grid, block, 0, p.stream, a);
+                        },
+                        vec, p.nt != 0, periodic != 0);
+                } else {
+                    select_variant(
+                        [&](auto V, auto N, auto BD, auto PER) {
+                            if constexpr (PER.value) hipLaunchKernelGGL((irf_cols_periodic_kernel<T, V.value, N.value, BD.value>), grid, block, 0, p.stream, a, period);
+                            else hipLaunchKernelGGL((irf_cols_kernel<T, V.value, N.value, BD.value>), grid, block, 0, p.stream, a);
+                        },
+                        vec, p.nt != 0, bounded, periodic != 0);
+                }
+            });
+            if (rc) return rc;
+        }
+        return VP_ERR_OK;
+    };
+    if (int rc = run(UNSHIFTED, p.irf, p.irf_stride)) return rc;
+    const int delta = irf_shift_param(p.model);
+    if (delta < 0) return VP_ERR_OK;
+    if (!p.irf_g || !p.irf_dg) return VP_ERR_INVALID;
+    const bool want_dg = p.dphi && is_free(delta);
+    if (int rc = irf_resample(p, delta, want_dg)) return rc;
+    if (int rc = run(SHIFT_VALUE, p.irf_g, p.irf_gs)) return rc;
+    if (want_dg)
+        if (int rc = run(SHIFT_DELTA, p.irf_dg, p.irf_gs)) return rc;
     return VP_ERR_OK;
 }
 

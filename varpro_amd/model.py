@@ -35,15 +35,26 @@ class basis:
     # ... with the response repeating every period T >= m dt (BatchProblem(..., irf_period=) / set_irf_period; default: the
     # record is one period): the steady state of the pulse train, for decays that outlast the laser period
     EXP_DECAY_IRF_PERIODIC = 11  # sum_{p>=0} sum_k irf_k rho^(i-k+pP), P = T/dt   (terms with i-k+pP >= 0)
+    # ... on the response SHIFTED by delta (grid units, positive: later; the last parameter of the function): kinds 9 - 11 on
+    # g_i = r(i - delta/dt), r the Catmull-Rom cubic through the samples, zero outside the record (irf_shifted below).  All
+    # shifted functions of a model name the SAME delta, and no other function may depend on it
+    EXP_DECAY_IRF_SHIFT = 12           # kind 9 on g       (p0 = tau, p1 = delta)
+    IRF_SHIFT = 13                     # g_i               (p0 = delta): the scattered-light term, shifted
+    EXP_DECAY_IRF_PERIODIC_SHIFT = 14  # kind 11 on g      (p0 = tau, p1 = delta)
     ARITY = {CONST: 0, EXP_DECAY: 1, EXP_RATE: 1, EXP_COS: 2, SIN_PHASE: 2, GAUSS: 2, LORENTZ: 2, LINEAR: 0,
-             EXP_DECAY_IRF: 1, IRF: 0, EXP_DECAY_IRF_PERIODIC: 1}
+             EXP_DECAY_IRF: 1, IRF: 0, EXP_DECAY_IRF_PERIODIC: 1, EXP_DECAY_IRF_SHIFT: 2, IRF_SHIFT: 1,
+             EXP_DECAY_IRF_PERIODIC_SHIFT: 2}
     NAME = {CONST: "const", EXP_DECAY: "exp_decay", EXP_RATE: "exp_rate", EXP_COS: "exp_cos", SIN_PHASE: "sin_phase",
             GAUSS: "gauss", LORENTZ: "lorentz", LINEAR: "linear", EXP_DECAY_IRF: "exp_decay_irf", IRF: "irf",
-            EXP_DECAY_IRF_PERIODIC: "exp_decay_irf_periodic"}
+            EXP_DECAY_IRF_PERIODIC: "exp_decay_irf_periodic", EXP_DECAY_IRF_SHIFT: "exp_decay_irf_shift",
+            IRF_SHIFT: "irf_shift", EXP_DECAY_IRF_PERIODIC_SHIFT: "exp_decay_irf_periodic_shift"}
+    # kinds that read the response shifted, and those with a period
+    SHIFT_KINDS = (EXP_DECAY_IRF_SHIFT, IRF_SHIFT, EXP_DECAY_IRF_PERIODIC_SHIFT)
+    PERIODIC_KINDS = (EXP_DECAY_IRF_PERIODIC, EXP_DECAY_IRF_PERIODIC_SHIFT)
     # kinds that need the instrument response
-    IRF_KINDS = (EXP_DECAY_IRF, IRF, EXP_DECAY_IRF_PERIODIC)
+    IRF_KINDS = (EXP_DECAY_IRF, IRF, EXP_DECAY_IRF_PERIODIC) + SHIFT_KINDS
     # kinds whose columns the device evaluates into memory (a device-column handle, include/varpro_hip.h)
-    DEVICE_COLUMN = (GAUSS, LORENTZ, LINEAR, EXP_DECAY_IRF, IRF, EXP_DECAY_IRF_PERIODIC)
+    DEVICE_COLUMN = (GAUSS, LORENTZ, LINEAR, EXP_DECAY_IRF, IRF, EXP_DECAY_IRF_PERIODIC) + SHIFT_KINDS
 
 
 def uniform_step(x, what="grid"):
@@ -128,11 +139,48 @@ def irf_columns(irf, dt, tau, period=None):
         return F, (dt / (tau * tau)) * H
 
 
+def irf_shifted(irf, dt, delta):
+    """numpy mirror of the resample kernel (vp_irf_shift.hpp) in the dtype of irf: (g, g') with g_i = r(i - s), s = delta/dt,
+    r the Catmull-Rom cubic through the samples and zero outside the record, g' = dg/ddelta (include/varpro_hip.h,
+    "Shifted IRF reconvolution"):  o = floor(-s), f = -s - o,  g_i = sum_{a=-1..2} w_a(f) irf_{i+o+a},
+    g'_i = -(1/dt) sum_a w'_a(f) irf_{i+o+a}.  A non-finite s gives NaN, |s| >= m + 2 exact zeros, delta = 0 the response."""
+    irf = np.asarray(irf)
+    T = irf.dtype.type
+    m = irf.size
+    with np.errstate(all="ignore"):
+        dt = T(dt)
+        ns = -(T(delta) / dt)
+        if not abs(ns) < T(m + 2):
+            v = T(0) if np.isfinite(ns) else T(np.nan)
+            return np.full(m, v, irf.dtype), np.full(m, v, irf.dtype)
+        fl = np.floor(ns)
+        o, f = int(fl), T(ns - fl)
+        h, ff = T(0.5), f * f
+        w = (h * (f * ((T(2) - f) * f - T(1))), h * (ff * (T(3) * f - T(5)) + T(2)),
+             h * (f * ((T(4) - T(3) * f) * f + T(1))), h * (ff * (f - T(1))))
+        d = (h * ((T(4) - T(3) * f) * f - T(1)), h * (f * (T(9) * f - T(10))),
+             h * ((T(8) - T(9) * f) * f + T(1)), h * (f * (T(3) * f - T(2))))
+        pad = np.zeros(3 * m + 8, irf.dtype)  # irf_k at pad[k + m + 4]: every tap of |o| <= m + 2 is inside
+        pad[m + 4:2 * m + 4] = irf
+        taps = [pad[m + 4 + o + a:2 * m + 4 + o + a] for a in (-1, 0, 1, 2)]
+        g = ((w[0] * taps[0] + w[1] * taps[1]) + w[2] * taps[2]) + w[3] * taps[3]
+        dg = -(((d[0] * taps[0] + d[1] * taps[1]) + d[2] * taps[2]) + d[3] * taps[3]) / dt
+        return g.astype(irf.dtype), dg.astype(irf.dtype)
+
+
 def _kind_columns(kind, x, p0, p1, irf=None, irf_period=None):
     """numpy mirror of one basis kind: (f, [df/dp0, df/dp1][:arity]) on the grid x (include/varpro_hip.h)"""
     if kind in basis.IRF_KINDS:
         if irf is None:
             raise ModelError("the model has an IRF reconvolution kind and no instrument response (model.irf)")
+        if kind in basis.SHIFT_KINDS:  # the unshifted kind on g; d/ddelta: its value column on g'
+            dt = uniform_step(x)
+            g, dg = irf_shifted(np.asarray(irf, dtype=x.dtype), dt, p0 if kind == basis.IRF_SHIFT else p1)
+            if kind == basis.IRF_SHIFT:
+                return g, [dg]
+            period = (irf_period or 0.0) if kind == basis.EXP_DECAY_IRF_PERIODIC_SHIFT else None
+            f, dtau = irf_columns(g, dt, p0, period)
+            return f, [dtau, irf_columns(dg, dt, p0, period)[0]]
         if kind == basis.IRF:
             return np.array(irf, dtype=x.dtype), []
         period = (irf_period or 0.0) if kind == basis.EXP_DECAY_IRF_PERIODIC else None
@@ -497,6 +545,20 @@ class SeparableModelBuilder:
             if n not in used:
                 raise ModelBuildError("UnusedParameter", "Model depends on parameter '%s', but none of its functions "
                                       "use it." % n)
+        # one response, one shift: every shifted function names the same delta, nothing else depends on it
+        deltas = [(f["params"][-1], f["kind"]) for f in self._functions if f["kind"] in basis.SHIFT_KINDS]
+        if deltas:
+            for name, kind in deltas:
+                if name != deltas[0][0]:
+                    raise ModelBuildError("SeveralIrfShifts", "the functions of kind %s and %s name different shift parameters "
+                                          "'%s' and '%s': a model has one response and one shift"
+                                          % (basis.NAME[deltas[0][1]], basis.NAME[kind], deltas[0][0], name))
+            for f in self._functions:
+                others = f["params"][:-1] if f["kind"] in basis.SHIFT_KINDS else f["params"]
+                if deltas[0][0] in others:
+                    raise ModelBuildError("IrfShiftShared", "the shift parameter '%s' of kind %s is also a parameter of a function "
+                                          "of kind %s: no other function may depend on it"
+                                          % (deltas[0][0], basis.NAME[deltas[0][1]], basis.NAME[f["kind"]]))
         if self._x is None:
             raise ModelBuildError("MissingX", "Missing vector for independent variable x")
         if any(f["kind"] in basis.IRF_KINDS for f in self._functions):

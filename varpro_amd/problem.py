@@ -151,7 +151,7 @@ class SeparableProblemBuilder:
                     % (x_len, tuple(self._irf.shape)))
             self._model.irf = self._irf.copy()  # (the model surface -- eval / eval_partial_deriv -- mirrors it on the host)
         if self._irf_period is not None:
-            if basis.EXP_DECAY_IRF_PERIODIC not in self._model.kinds:
+            if not any(k in basis.PERIODIC_KINDS for k in self._model.kinds):
                 raise SeparableProblemBuilderError("UnexpectedIrfPeriod", "the model has no basis.EXP_DECAY_IRF_PERIODIC function")
             try:
                 self._model.irf_period = check_irf_period(self._irf_period, x_len, uniform_step(self._model.x))
