@@ -839,8 +839,6 @@ int read_sum4(vp_batch *h, double out[4]) {
     return VP_ERR_OK;
 }
 
-bool has_mrhs_set(const KernelEntry *k) { return k->mrhs_factor && k->mrhs_stream && k->mrhs_lm && k->mrhs_finish; }
-
 // run the evaluate kernel at h->d_alpha; any output may be null
 int run_evaluate(vp_batch *h, void *r_dev, void *J_dev, void *C_dev) {
     if (h->external && !h->ext_phi)
@@ -983,7 +981,7 @@ int mrhs_enqueue_iteration(MrhsFit &f, LaunchParams &lp) {
     if (h->rhs_allreduce) {
         const int64_t total = h->B * f.nacc;
         hipLaunchKernelGGL(mrhs_reduce_partials_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                           lp.stream, (const double *)h->mrhs.acc, mrhs_gx(h->S, h->kern->mrhs_gx_cap > 0 ? h->kern->mrhs_gx_cap : 256), f.nacc, h->B,
+                           lp.stream, (const double *)h->mrhs.acc, mrhs_gx(h->S, h->kern->gx_cap()), f.nacc, h->B,
                            h->d_mrhs_tot);
         VP_HIP(hipGetLastError());
         if (h->rhs_allreduce(h->d_mrhs_tot, total, (void *)lp.stream, h->rhs_allreduce_user) != 0)
@@ -1538,7 +1536,7 @@ static int batch_init(vp_batch *h, const void *t, const void *Y, const void *w, 
         if (int rc = h->alloc(ws.statusA, (size_t)B * sizeof(int32_t))) return rc;
         // partial-sum slots of the MODE 0 pass (the only writer): gx is fixed per handle -- min(ceil(S/8), the kernel set's
         // cap) -- not the upper bound VP_MRHS_GX_MAX (B = 70000, S = 2 needs 1 slot per problem, not 512)
-        const int gx_acc = mrhs_gx(S, h->kern->mrhs_gx_cap > 0 ? h->kern->mrhs_gx_cap : 256);
+        const int gx_acc = mrhs_gx(S, h->kern->gx_cap());
         if (gx_acc > VP_MRHS_GX_MAX) return fail(VP_ERR_INVALID, "internal: partial-sum slots per problem exceed VP_MRHS_GX_MAX");
         if (int rc = h->alloc(ws.acc, (size_t)B * gx_acc * (1 + n_ * n_ + p_) * sizeof(double))) return rc;
         if (int rc = h->alloc(ws.lm_state, (size_t)B * h->kern->mrhs_state_bytes)) return rc;
@@ -1629,8 +1627,7 @@ static int batch_create_impl(vp_batch **out, const vp_model_desc *model, int dty
 
     // a specialised (register-resident) kernel set if one is instantiated for this (dtype, model, m), else the generic
     // fallback kernels (vp_generic.hpp): any descriptor, any m -- slower, but never a CPU path and never "unsupported"
-    const KernelEntry *kern = ext ? external_kernels(dtype, model->n_basis, model->n_params, ext->np, m, S)
-                                  : find_kernels(dtype, *model, m, S, w != nullptr);
+    const KernelEntry *kern = ext ? external_kernels(dtype) : find_kernels(dtype, *model, m, S, w != nullptr);
     if (!ext && (flags & VP_FLAG_STREAM_ROWS)) { // only the length-agnostic sets (capacity 2^26 rows) pass this length
         const KernelEntry *ks = find_kernels(dtype, *model, (int64_t)1 << 24, S, w != nullptr);
         if (ks) kern = ks;
@@ -2201,7 +2198,7 @@ int rescue_refit(vp_batch *h, const LaunchParams &fit_params) {
     // list's other counter
     p.gen_list_first = 0;
     p.last_fit = nullptr; // (the record names the fit's own launch, not the re-fit of what it flagged)
-    if (launch_fn fast = find_fit_rescue(h->kern->fit_single)) {
+    if (launch_fn fast = h->kern->fit_rescue) {
         const int rc = fast(p);
         if (rc == VP_ERR_OK) p.gen_list_first = kFitRescueGrid;
         else if (rc != VP_ERR_UNSUPPORTED) return rc;
@@ -2844,10 +2841,10 @@ int vp_statistics(vp_batch *h, void *cov_out, double *reduced_chi2_out, void *co
     p.C_out = h->d_C;
     p.cost_out = h->d_cost;
     p.status = h->d_status;
-    p.Phi_out = cov.dptr;
-    p.dPhi_out = chi2.dptr;
-    p.r_out = sig.dptr;
-    p.J_out = st.dev;
+    p.cov_out = cov.dptr;
+    p.chi2_out = (double *)chi2.dptr;
+    p.sigma_out = sig.dptr;
+    p.stats_status = st.dev;
     int rc = h->kern->stats(p);
     if (rc == VP_ERR_OK) rc = cov.finish(h);
     if (rc == VP_ERR_OK) rc = chi2.finish(h);
@@ -3059,10 +3056,6 @@ int vp_synchronize(vp_batch *h) {
 // ---- registry ------------------------------------------------------------------------------------------
 namespace vp {
 
-std::vector<RescueEntry> &rescue_registry() {
-    static std::vector<RescueEntry> r;
-    return r;
-}
 std::vector<KernelEntry> &registry() {
     static std::vector<KernelEntry> r;
     return r;

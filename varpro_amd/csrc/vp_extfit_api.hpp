@@ -2,6 +2,7 @@
 // (vp_extfit.hpp): what vp_api.hip calls and vp_inst_ext.hip implements.  Kept out of vp_registry.hpp: every instantiation
 // file includes that one.
 #pragma once
+#include <hip/hip_runtime.h>
 #include "vp_registry.hpp"
 
 namespace vp {

@@ -1304,10 +1304,10 @@ template <typename T> int launch_stats(const LaunchParams &p) {
     sa.C = (const T *)p.C_out;
     sa.cost = p.cost_out;
     sa.status_in = p.status;
-    sa.cov_out = (T *)p.Phi_out;
-    sa.chi2_out = (double *)p.dPhi_out;
-    sa.sigma_out = (T *)p.r_out;
-    sa.status_out = (int32_t *)p.J_out;
+    sa.cov_out = (T *)p.cov_out;
+    sa.chi2_out = p.chi2_out;
+    sa.sigma_out = (T *)p.sigma_out;
+    sa.status_out = p.stats_status;
     if (sa.g.B <= 0) return VP_ERR_OK;
     hipLaunchKernelGGL((gen_stats_kernel<T>), dim3((unsigned)p.gen_blocks), dim3(TB), 0, p.stream, sa);
     return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;

@@ -6,25 +6,32 @@
 #include "vp_generic.hpp"
 #include "vp_registry.hpp"
 
-#define VP_BLK_CAT_(a, b) a##b
-#define VP_BLK_CAT(a, b) VP_BLK_CAT_(a, b)
 namespace vp {
 namespace blk {
 template <typename T, class M> int launch_evaluate_entry(const LaunchParams &p) {
     return launch_evaluate<T, M>(p, &::vp::gen::launch_evaluate<T>);
 }
 } // namespace blk
+template <typename T, class M> KernelEntry blocked_set(int dtype, int family, int a, int b, int c) {
+    KernelEntry e{};
+    e.dtype = dtype; e.family = family; e.a = a; e.b = b; e.c = c; e.R = 1 << 20; e.W = 1;
+    e.evaluate = &blk::launch_evaluate_entry<T, M>;
+    e.basis = &gen::launch_basis<T>;
+    e.fit_single = &blk::launch_fit<T, M>;
+    if constexpr (fit_rescue_v<T, M>) e.fit_rescue = &blk::launch_fit_rescue<T, M>;
+    e.best_fit = &gen::launch_best_fit<T>;
+    e.mrhs_state_bytes = gen::mrhs_lm_state_bytes<T>();
+    e.stats = &gen::launch_stats<T>;
+    e.mrhs_fit_whole = &gen::launch_mrhs_fit<T>;
+    e.uses_gen_ws = 1;
+    return e;
+}
 } // namespace vp
-#define VP_BLK_ENTRY(T, DT, FAM, KA, KB, KC, MODEL)                                                                    \
-    static ::vp::Registrar VP_BLK_CAT(vp_blk_reg_, __COUNTER__)(::vp::KernelEntry{                                    \
-        DT, FAM, KA, KB, KC, 1 << 20, 1, &::vp::blk::launch_evaluate_entry<T, MODEL>, &::vp::gen::launch_basis<T>, nullptr, \
-        &::vp::blk::launch_fit<T, MODEL>, &::vp::gen::launch_best_fit<T>, nullptr, nullptr, nullptr, nullptr,          \
-        ::vp::gen::mrhs_lm_state_bytes<T>(), &::vp::gen::launch_stats<T>, &::vp::gen::launch_mrhs_fit<T>, 0, 0, 0, 1});
+
+#define VP_BLK_CAT_(a, b) a##b
+#define VP_BLK_CAT(a, b) VP_BLK_CAT_(a, b)
+#define VP_BLK_REGISTER(...) static ::vp::Registrar VP_BLK_CAT(vp_blk_reg_, __COUNTER__)(__VA_ARGS__);
 #define VP_REGISTER_BLOCKED_MULTIEXP(T, DT, NEXP, OFF)                                                                 \
-    VP_BLK_ENTRY(T, DT, ::vp::FAMILY_MULTIEXP, NEXP, OFF, 0, VP_BLK_ME(NEXP, OFF))                                     \
-    static ::vp::RescueRegistrar VP_BLK_CAT(vp_blk_resc_, __COUNTER__)(                                               \
-        &::vp::blk::launch_fit<T, VP_BLK_ME(NEXP, OFF)>,                                                              \
-        ::vp::fit_rescue_v<T, VP_BLK_ME(NEXP, OFF)> ? &::vp::blk::launch_fit_rescue<T, VP_BLK_ME(NEXP, OFF)> : nullptr);
-#define VP_BLK_ME(NEXP, OFF) ::vp::MultiExpModel<NEXP, (OFF) != 0>
-#define VP_REGISTER_BLOCKED_RT(T, DT, NN, QQ, PP) VP_BLK_ENTRY(T, DT, ::vp::FAMILY_RT, NN, QQ, PP, VP_BLK_RT(NN, QQ, PP))
-#define VP_BLK_RT(NN, QQ, PP) ::vp::RtModel<NN, QQ, PP>
+    VP_BLK_REGISTER(::vp::blocked_set<T, ::vp::MultiExpModel<NEXP, (OFF) != 0>>(DT, ::vp::FAMILY_MULTIEXP, NEXP, OFF, 0))
+#define VP_REGISTER_BLOCKED_RT(T, DT, NN, QQ, PP)                                                                      \
+    VP_BLK_REGISTER(::vp::blocked_set<T, ::vp::RtModel<NN, QQ, PP>>(DT, ::vp::FAMILY_RT, NN, QQ, PP))

@@ -11,21 +11,22 @@
 
 namespace vp {
 namespace {
-int ext_evaluate_f64(const LaunchParams &p) { return ext::launch_evaluate<double>(p, &gen::launch_evaluate<double>); }
-int ext_evaluate_f32(const LaunchParams &p) { return ext::launch_evaluate<float>(p, &gen::launch_evaluate<float>); }
+template <typename T> int ext_evaluate(const LaunchParams &p) { return ext::launch_evaluate<T>(p, &gen::launch_evaluate<T>); }
+
+// (no basis / fit entries: the device cannot evaluate the model; vp_api.hip refuses those calls)
+template <typename T> KernelEntry external_set(int dtype) {
+    KernelEntry e{};
+    e.dtype = dtype; e.family = FAMILY_GENERIC; e.W = 1;
+    e.evaluate = &ext_evaluate<T>;
+    e.best_fit = &gen::launch_best_fit<T>;
+    e.stats = &gen::launch_stats<T>;
+    e.uses_gen_ws = 1;
+    return e;
+}
 } // namespace
 
-const KernelEntry *external_kernels(int dtype, int n, int q, int np, int64_t m, int64_t S) {
-    (void)n;
-    (void)q;
-    (void)np;
-    (void)m;
-    (void)S;
-    // (no basis / fit entries: the device cannot evaluate the model; vp_api.hip refuses those calls)
-    static const KernelEntry f64{VP_F64, FAMILY_GENERIC, 0, 0, 0, 0, 1, &ext_evaluate_f64, nullptr, nullptr, nullptr,
-                                 &gen::launch_best_fit<double>, nullptr, nullptr, nullptr, nullptr, 0, &gen::launch_stats<double>, nullptr, 0, 0, 0, 1};
-    static const KernelEntry f32{VP_F32, FAMILY_GENERIC, 0, 0, 0, 0, 1, &ext_evaluate_f32, nullptr, nullptr, nullptr,
-                                 &gen::launch_best_fit<float>, nullptr, nullptr, nullptr, nullptr, 0, &gen::launch_stats<float>, nullptr, 0, 0, 0, 1};
+const KernelEntry *external_kernels(int dtype) {
+    static const KernelEntry f64 = external_set<double>(VP_F64), f32 = external_set<float>(VP_F32);
     return dtype == VP_F64 ? &f64 : &f32;
 }
 

@@ -42,13 +42,17 @@ struct LaunchParams {
     const void *yw;     // [B][S][m] weighted data
     const void *alpha;  // [B][q]
     void *alpha_out;    // fit: [B][q]
-    void *r_out;        // [B][S][m] or NULL
+    void *r_out;        // [B][S][m] or NULL (best_fit: the fitted curve, an array of the residual's shape and type)
     void *J_out;        // [B][q][S][m] or NULL
     void *C_out;        // [B][S][n] or NULL
     double *cost_out;   // [B*S] partial costs (per problem and RHS) or NULL
     int32_t *status;    // [B*S] or NULL
     void *Phi_out;      // basis: [B][n or n_alpha][m]
     void *dPhi_out;     // basis: [B][p][m]
+    void *cov_out;      // statistics: [B][n+q][n+q]
+    double *chi2_out;   // statistics: [B] reduced chi^2
+    void *sigma_out;    // statistics: [B][m] confidence band or NULL
+    int32_t *stats_status; // statistics: [B] or NULL
     vp_report *report;  // fit: [B]
     const vp_lm_opts *opts;
     double *trace;      // fit diagnostics: [B][trace_rows][q+4] or NULL

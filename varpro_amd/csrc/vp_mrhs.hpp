@@ -24,6 +24,7 @@
 // r = y - Q P_n Q^T y (the Jacobian keeps the full Q, like the reference keeps the full U).
 #pragma once
 #include "vp_lm_core.hpp"
+#include "vp_registry.hpp"
 
 namespace vp {
 
@@ -1368,7 +1369,7 @@ template <class M> inline void pair_maps(const vp_model_desc &d, int (&pb)[M::P 
 // workgroups per problem of the streaming kernel: one persistent 8-wave workgroup per CU at most (its LDS copy
 // of Q and G is ~100 KiB)
 constexpr int VP_MRHS_GX_MAX = 512; // partial-sum slots per problem the handle allocates
-inline int mrhs_gx(int64_t S, int cap = 256) {
+inline int mrhs_gx(int64_t S, int cap = kMrhsGxCapDefault) {
     int64_t gx = (S + 7) / 8;
     if (gx > cap) gx = cap;
     if (gx < 1) gx = 1;
@@ -1378,9 +1379,9 @@ inline int mrhs_gx(int64_t S, int cap = 256) {
 // two 4-wave workgroups per CU, the one-wave-per-column kernel one 8-wave workgroup
 template <typename T, int R> constexpr int mrhs_gx_cap() {
 #ifndef VP_NO_MRHS_DMA
-    return (sizeof(T) == 8 && R == 32) ? 512 : 256;
+    return (sizeof(T) == 8 && R == 32) ? 512 : kMrhsGxCapDefault;
 #else
-    return 256;
+    return kMrhsGxCapDefault;
 #endif
 }
 

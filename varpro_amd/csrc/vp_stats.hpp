@@ -158,10 +158,10 @@ template <typename T, class M, int R, int W = 1> int launch_stats(const LaunchPa
     a.C = (const T *)p.C_out;
     a.cost = p.cost_out;
     a.status_in = p.status;
-    a.cov_out = (T *)p.Phi_out;
-    a.chi2_out = (double *)p.dPhi_out;
-    a.sigma_out = (T *)p.r_out;
-    a.status_out = (int32_t *)p.J_out;
+    a.cov_out = (T *)p.cov_out;
+    a.chi2_out = p.chi2_out;
+    a.sigma_out = (T *)p.sigma_out;
+    a.status_out = p.stats_status;
     a.m = p.m;
     a.B = p.B;
     a.t_stride = p.t_stride;
