@@ -34,8 +34,8 @@ def fit_case_id(fc):
 
 # ---- launch_fit's three inequalities, restated once ------------------------------------------------------------------------
 def padding_class(m, R, W):
-    """the instantiation by length of launch_fit / launch_fit2 (vp_fit.hpp, vp_fit2.hpp) for an UNWEIGHTED problem:
-    1 if m == 64 R W; else 2 if R > 2 and m > 64 (R - 2) W; else 0"""
+    """padding_variant (vp_fit.hpp), the one rule launch_fit and launch_fit2 pick their instantiation by length with for an
+    UNWEIGHTED problem, restated: 1 if m == 64 R W; else 2 if R > 2 and m > 64 (R - 2) W; else 0"""
     if m == 64 * R * W:
         return 1
     if R > 2 and m > 64 * (R - 2) * W:

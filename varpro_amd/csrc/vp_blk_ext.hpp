@@ -410,7 +410,7 @@ template <typename T, int N, int P> int launch_ext_stream(const ext::ExtArgs<T> 
     // not by HBM; direct route 0.86 ms at 2 048, 0.94 at 1 536, 1.02 at 1 024, 1.52 at 512: a wave holds one block (24 KB) in
     // flight, fewer waves are fewer bytes in flight)
     hipLaunchKernelGGL((ext_stream_evaluate_kernel<T, N, P, RB>), dim3((unsigned)a.nprob), dim3(64), snap, stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 } // namespace blk

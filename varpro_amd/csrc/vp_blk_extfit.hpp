@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(64, (ext_fit_stream_waves<T, N + 1 + P, RB>())
 template <typename T, int N, int P, int Q> int launch_fit_stream_eval(const ext::ExtFitArgs<T> &a, hipStream_t stream) {
     constexpr int RB = ext_fit_stream_rows<T, N + 1 + P>();
     hipLaunchKernelGGL((ext_fit_stream_eval_kernel<T, N, P, Q, RB>), dim3((unsigned)a.grid_problems), dim3(64), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 } // namespace blk

@@ -345,13 +345,7 @@ __device__ __forceinline__ bool blk_fit_problem(const FitArgs<T, M> &a, const in
     const T *yp = a.yw + b * (int64_t)m;
 
     LmVars<T, N, Q> S;
-    LmOpts<T> opt;
-    opt.ftol = a.ftol;
-    opt.xtol = a.xtol;
-    opt.gtol = a.gtol;
-    opt.stepbound = a.stepbound;
-    opt.patience = a.patience;
-    opt.scale_diag = a.scale_diag;
+    const LmOpts<T> opt = a.lm;
     {
         T a0[Q];
 #pragma unroll
@@ -898,59 +892,18 @@ template <typename T, class M> int launch_evaluate(const LaunchParams &p, int (*
     const size_t snap = want_rj ? eval_snap_bytes<T, M, RB>(p.m) : 0;
     if (snap > kEvalSnapMax || p.m < M::N) return fallback(p); // (m < N: the padded handles of vp_batch_create stay generic)
     EvalArgs<T, M> a;
-    if (!bind_model(*p.model, a.mdl)) return VP_ERR_UNSUPPORTED;
-    a.t = (const T *)p.t;
-    a.w = (const T *)p.w;
-    a.yw = (const T *)p.yw;
-    a.alpha = (const T *)p.alpha;
-    a.r_out = (T *)p.r_out;
-    a.J_out = (T *)p.J_out;
-    a.C_out = (T *)p.C_out;
-    a.cost_out = p.cost_out;
-    a.status = p.status;
-    a.m = p.m;
-    a.S = p.S;
-    a.nprob = p.B * p.S;
-    a.t_stride = p.t_stride;
-    a.w_stride = p.w_stride;
-    a.eps = (T)p.eps;
-    a.grid_uniform = p.grid_uniform;
+    if (!fill_eval_args(p, a)) return VP_ERR_UNSUPPORTED;
     if (a.nprob <= 0) return VP_ERR_OK;
     const size_t lds = (size_t)2 * (p.w ? 3 : 2) * 64 * RB * sizeof(T) + snap;
     (void)sizeof(Ring);
     if (p.w) hipLaunchKernelGGL((blk_evaluate_kernel<T, M, RB, true>), dim3((unsigned)a.nprob), dim3(64), lds, p.stream, a);
     else hipLaunchKernelGGL((blk_evaluate_kernel<T, M, RB, false>), dim3((unsigned)a.nprob), dim3(64), lds, p.stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 template <typename T, class M> int launch_fit(const LaunchParams &p) {
     FitArgs<T, M> a;
-    if (!bind_model(*p.model, a.mdl)) return VP_ERR_UNSUPPORTED;
-    sweep_invariant_first(a.mdl); // (run-time-descriptor models: constant columns first in the sweep, vp_model.hpp)
-    a.t = (const T *)p.t;
-    a.w = (const T *)p.w;
-    a.yw = (const T *)p.yw;
-    a.alpha = (T *)p.alpha_out;
-    a.C_out = (T *)p.C_out;
-    a.cost_out = p.cost_out;
-    a.status = p.status;
-    a.report = p.report;
-    a.m = p.m;
-    a.B = p.B;
-    a.t_stride = p.t_stride;
-    a.w_stride = p.w_stride;
-    a.eps = (T)p.eps;
-    a.ftol = (T)p.opts->ftol;
-    a.xtol = (T)p.opts->xtol;
-    a.gtol = (T)p.opts->gtol;
-    a.stepbound = (T)p.opts->stepbound;
-    a.patience = p.opts->patience;
-    a.scale_diag = p.opts->scale_diag;
-    a.trace = p.trace;
-    a.trace_rows = p.trace_rows;
-    a.grid_uniform = p.grid_uniform;
-    a.rescue = p.rescue;
-    a.rescue_slot = p.rescue_slot;
+    if (!fill_fit_args(p, a)) return VP_ERR_UNSUPPORTED;
     if (a.B <= 0) return VP_ERR_OK;
     if (p.rescue_used) *p.rescue_used = 1;
     constexpr int RB = block_rows<T, M::N + 1 + M::P, M::kStatic>();
@@ -991,7 +944,7 @@ template <typename T, class M> int launch_fit(const LaunchParams &p) {
     }
 #undef VP_BLK_FIT
 #undef VP_BLK_FIT_TC
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 // the re-fit launch of the streamed kernels' flagged problems: one wave per problem at the base block height (any m, grid values
@@ -1003,31 +956,7 @@ template <typename T, class M> int launch_fit_rescue(const LaunchParams &p) {
     } else {
         if (p.w || p.t_stride != 0 || !p.rescue) return VP_ERR_UNSUPPORTED;
         FitArgs<T, M> a;
-        if (!bind_model(*p.model, a.mdl)) return VP_ERR_UNSUPPORTED;
-        a.t = (const T *)p.t;
-        a.w = nullptr;
-        a.yw = (const T *)p.yw;
-        a.alpha = (T *)p.alpha_out;
-        a.C_out = (T *)p.C_out;
-        a.cost_out = p.cost_out;
-        a.status = p.status;
-        a.report = p.report;
-        a.m = p.m;
-        a.B = p.B;
-        a.t_stride = 0;
-        a.w_stride = 0;
-        a.eps = (T)p.eps;
-        a.ftol = (T)p.opts->ftol;
-        a.xtol = (T)p.opts->xtol;
-        a.gtol = (T)p.opts->gtol;
-        a.stepbound = (T)p.opts->stepbound;
-        a.patience = p.opts->patience;
-        a.scale_diag = p.opts->scale_diag;
-        a.trace = p.trace;
-        a.trace_rows = p.trace_rows;
-        a.grid_uniform = p.grid_uniform;
-        a.rescue = p.rescue;
-        a.rescue_slot = p.rescue_slot;
+        if (!fill_fit_args(p, a)) return VP_ERR_UNSUPPORTED; // (w null, t_stride 0 by the test above; w_stride is not read without w)
         constexpr int RB = block_rows<T, M::N + 1 + M::P, M::kStatic>();
         // (a flagged fit is a chain of ~70 evaluations nothing overlaps: four waves per problem shorten it ~3.5x where the
         // problem has the blocks for them -- 4.0 -> 1.2 ms behind a batch of 16 384 problems of 10 000 rows)
@@ -1035,11 +964,11 @@ template <typename T, class M> int launch_fit_rescue(const LaunchParams &p) {
         if constexpr (WM * (M::N + 1 + M::P) <= 128) {
             if (p.m >= VP_BLK_MULTI_MIN_BLOCKS * WM * 64 * RB) {
                 hipLaunchKernelGGL((blk_fit_kernel<T, M, RB, false, WM, false, true>), dim3(kFitRescueGrid), dim3(64 * WM), 0, p.stream, a);
-                return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+                return launch_status();
             }
         }
         hipLaunchKernelGGL((blk_fit_kernel<T, M, RB, false, 1, false, true>), dim3(kFitRescueGrid), dim3(64), 0, p.stream, a);
-        return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+        return launch_status();
     }
 }
 

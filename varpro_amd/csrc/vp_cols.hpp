@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "../../include/varpro_hip.h"
+#include "vp_kernels.hpp" // launch_status()
 #include "vp_model.hpp"
 
 namespace vp {
@@ -414,7 +415,7 @@ int launch_bounds_transform(void *x, const void *lo, const void *hi, int64_t bou
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
     if (to_internal) hipLaunchKernelGGL((bounds_map_kernel<T, true>), grid, block, 0, stream, (T *)x, (const T *)lo, (const T *)hi, bound_stride, q, total);
     else hipLaunchKernelGGL((bounds_map_kernel<T, false>), grid, block, 0, stream, (T *)x, (const T *)lo, (const T *)hi, bound_stride, q, total);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 // ---- what the launches of this header and of vp_irf.hpp share ----------------------------------------------------------

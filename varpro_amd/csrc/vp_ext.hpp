@@ -176,7 +176,7 @@ __global__ void __launch_bounds__(64 * W, (ext_waves<T, R, N, N + 1 + (WITH_D ? 
 template <typename T, int N, int P, int R, bool WITH_D, int W = 1> int launch_one(const ExtArgs<T> &a, hipStream_t stream) {
     hipLaunchKernelGGL((ext_evaluate_kernel<T, N, P, R, WITH_D, W>), dim3((unsigned)a.nprob), dim3(64 * W),
                        (size_t)group_xch_bytes<W>(), stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 // one row of the table of compiled shapes (vp_inst_ext*.hip)

@@ -464,11 +464,11 @@ template <typename T, int Q> __global__ void __launch_bounds__(64) ext_fit_lm_ke
 
 template <typename T, int N, int P, int Q, int R, int W> int launch_fit_eval(const ExtFitArgs<T> &a, hipStream_t stream) {
     hipLaunchKernelGGL((ext_fit_eval_kernel<T, N, P, Q, R, W>), dim3((unsigned)a.grid_problems), dim3(64 * W), group_xch_bytes<W>(), stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 template <typename T, int Q> int launch_fit_lm(const ExtFitArgs<T> &a, hipStream_t stream) {
     hipLaunchKernelGGL((ext_fit_lm_kernel<T, Q>), dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 // one row of the table of compiled evaluation shapes (vp_inst_extfit*.hip) ...

@@ -1066,9 +1066,7 @@ template <typename T, class M> struct FitArgs {
     int64_t B;
     int64_t t_stride, w_stride;
     T eps;
-    T ftol, xtol, gtol, stepbound;
-    int patience;
-    int scale_diag;
+    LmOpts<T> lm;
     double *trace;  // diagnostics (vp_fit_trace): [B][trace_rows][q+4] or null
     int trace_rows;
     int grid_uniform; // the handle's grids passed grid_check_kernel -> exp recurrence allowed
@@ -1191,7 +1189,7 @@ __device__ __forceinline__ bool fit_problem(const FitArgs<T, M> &a, const int64_
     int nfev = 0, term = VP_TERM_NOT_RUN;
     int st_best = VP_ST_NOT_EVALUATED;
     bool flagged = false; // handed to the re-fit launch (jac_not_finite)
-    const int max_fev = a.patience * (Q + 1);
+    const int max_fev = a.lm.patience * (Q + 1);
     const int mres = m; // number of residuals (S == 1)
     int trow = 0;
     auto trace_row = [&](const T(&xx)[Q], T fn, T ratio) {
@@ -1365,7 +1363,7 @@ __device__ __forceinline__ bool fit_problem(const FitArgs<T, M> &a, const int64_
                 for (int k = 0; k < N; ++k) cbest[k] = u.c[k];
                 T tmpv[Q];
 #pragma unroll
-                for (int k = 0; k < Q; ++k) tmpv[k] = a.scale_diag ? diag[k] * x[k] : x[k];
+                for (int k = 0; k < Q; ++k) tmpv[k] = a.lm.scale_diag ? diag[k] * x[k] : x[k];
                 xnorm = enorm_small<T, Q>(tmpv);
                 fnorm = fnorm1;
                 objective = T(0.5) * fnorm1 * fnorm1;
@@ -1377,8 +1375,8 @@ __device__ __forceinline__ bool fit_problem(const FitArgs<T, M> &a, const int64_
             int tcode = 0;
             if (fnorm <= num<T>::tiny) tcode = VP_TERM_RESIDUALS_ZERO;
             if (!tcode) {
-                const bool ftol_check = tabs(actred) <= a.ftol && prered <= a.ftol && ratio * T(0.5) <= T(1);
-                const bool xtol_check = delta <= a.xtol * xnorm;
+                const bool ftol_check = tabs(actred) <= a.lm.ftol && prered <= a.lm.ftol && ratio * T(0.5) <= T(1);
+                const bool xtol_check = delta <= a.lm.xtol * xnorm;
                 if (ftol_check || xtol_check)
                     tcode = (ftol_check && xtol_check) ? VP_TERM_CONVERGED_BOTH
                                                        : (ftol_check ? VP_TERM_CONVERGED_FTOL : VP_TERM_CONVERGED_XTOL);
@@ -1439,7 +1437,7 @@ __device__ __forceinline__ bool fit_problem(const FitArgs<T, M> &a, const int64_
                 term = VP_TERM_NUMERICAL;
                 break;
             }
-            if (uni(gnorm <= a.gtol)) {
+            if (uni(gnorm <= a.lm.gtol)) {
                 term = VP_TERM_ORTHOGONAL;
                 break;
             }
@@ -1447,17 +1445,17 @@ __device__ __forceinline__ bool fit_problem(const FitArgs<T, M> &a, const int64_
                 T tmpv[Q];
 #pragma unroll
                 for (int k = 0; k < Q; ++k) {
-                    if (a.scale_diag) diag[k] = (acnorm[k] == T(0)) ? T(1) : acnorm[k];
-                    tmpv[k] = a.scale_diag ? diag[k] * x[k] : x[k];
+                    if (a.lm.scale_diag) diag[k] = (acnorm[k] == T(0)) ? T(1) : acnorm[k];
+                    tmpv[k] = a.lm.scale_diag ? diag[k] * x[k] : x[k];
                 }
                 xnorm = enorm_small<T, Q>(tmpv);
                 if (uni(!is_finite(xnorm))) {
                     term = VP_TERM_NUMERICAL;
                     break;
                 }
-                delta = (xnorm == T(0)) ? a.stepbound : a.stepbound * xnorm;
+                delta = (xnorm == T(0)) ? a.lm.stepbound : a.lm.stepbound * xnorm;
                 first_update = false;
-            } else if (a.scale_diag) {
+            } else if (a.lm.scale_diag) {
 #pragma unroll
                 for (int k = 0; k < Q; ++k) diag[k] = tmax(diag[k], acnorm[k]);
             }
@@ -1560,10 +1558,19 @@ template <typename T, class M, int R, int W> constexpr size_t fit_lds_bytes(bool
     return (size_t)(weighted ? 3 : 2) * 64 * R * W * sizeof(T) + ((group_xch_bytes<W>() + 15) / 16) * 16 +
            (size_t)W * sizeof(LmState<T, M::N, M::Q>);
 }
-template <typename T, class M, int R, int W = 1> int launch_fit(const LaunchParams &p) {
-    FitArgs<T, M> a;
-    if (!bind_model(*p.model, a.mdl)) return VP_ERR_UNSUPPORTED;
-    sweep_invariant_first(a.mdl); // (run-time-descriptor models: constant columns first in the sweep, vp_model.hpp)
+// the fit kernels' argument record, filled in ONE place for every launcher of the resident and the blocked family (vp_fit2.hpp,
+// vp_block.hpp); false: the descriptor does not match M.  Run-time-descriptor models get their constant columns first in the
+// sweep (vp_model.hpp; the identity for static models, the only ones the re-fit and the slot launchers are built for).
+template <typename T, class M> inline bool fill_fit_args(const LaunchParams &p, FitArgs<T, M> &a) {
+    using A = FitArgs<T, M>;
+    static_assert(std::is_trivially_copyable_v<A>, "kernel argument records are filled byte-wise");
+    // the embedded options lie where six separate fields (four T, two int) lay: right behind eps, the trace pointer after them
+    static_assert(sizeof(LmOpts<T>) == 4 * sizeof(T) + 2 * sizeof(int) && offsetof(A, lm) == offsetof(A, eps) + sizeof(T) &&
+                      offsetof(A, trace) == (offsetof(A, lm) + sizeof(LmOpts<T>) + 7) / 8 * 8,
+                  "FitArgs: the layout the kernels were built for");
+    std::memset(&a, 0, sizeof a);
+    if (!bind_model(*p.model, a.mdl)) return false;
+    sweep_invariant_first(a.mdl);
     a.t = (const T *)p.t;
     a.w = (const T *)p.w;
     a.yw = (const T *)p.yw;
@@ -1577,34 +1584,44 @@ template <typename T, class M, int R, int W = 1> int launch_fit(const LaunchPara
     a.t_stride = p.t_stride;
     a.w_stride = p.w_stride;
     a.eps = (T)p.eps;
-    a.ftol = (T)p.opts->ftol;
-    a.xtol = (T)p.opts->xtol;
-    a.gtol = (T)p.opts->gtol;
-    a.stepbound = (T)p.opts->stepbound;
-    a.patience = p.opts->patience;
-    a.scale_diag = p.opts->scale_diag;
+    a.lm = lm_opts_from<T>(*p.opts);
     a.trace = p.trace;
     a.trace_rows = p.trace_rows;
     a.grid_uniform = p.grid_uniform;
     a.rescue = p.rescue;
     a.rescue_slot = p.rescue_slot;
+    return true;
+}
+
+// the instantiation by length of the wave and the slot kernel for an UNWEIGHTED problem (PADM): 1 = every row valid, 2 = only
+// the last register pair can hold padding rows, 0 = any length
+inline int padding_variant(int m, int R, int W) {
+    if (m == 64 * R * W) return 1;
+    if (R > 2 && m > 64 * (R - 2) * W) return 2;
+    return 0;
+}
+
+template <typename T, class M, int R, int W = 1> int launch_fit(const LaunchParams &p) {
+    FitArgs<T, M> a;
+    if (!fill_fit_args(p, a)) return VP_ERR_UNSUPPORTED;
     if (a.B <= 0) return VP_ERR_OK;
     if (p.rescue_used) *p.rescue_used = 1;
     const size_t lds = fit_lds_bytes<T, M, R, W>(p.w != nullptr);
+    const int padm = padding_variant(p.m, R, W);
     if (p.w) {
         record_fit(p, kFitKernelWave, 0, true);
         hipLaunchKernelGGL((fit_kernel<T, M, R, W, true>), dim3((unsigned)a.B), dim3(64 * W), lds, p.stream, a);
-    } else if (p.m == 64 * R * W) {
+    } else if (padm == 1) {
         record_fit(p, kFitKernelWave, 1, false);
         hipLaunchKernelGGL((fit_kernel<T, M, R, W, false, 1>), dim3((unsigned)a.B), dim3(64 * W), lds, p.stream, a);
-    } else if (R > 2 && p.m > 64 * (R - 2) * W) {
+    } else if (padm == 2) {
         record_fit(p, kFitKernelWave, 2, false);
         hipLaunchKernelGGL((fit_kernel<T, M, R, W, false, 2>), dim3((unsigned)a.B), dim3(64 * W), lds, p.stream, a);
     } else {
         record_fit(p, kFitKernelWave, 0, false);
         hipLaunchKernelGGL((fit_kernel<T, M, R, W, false>), dim3((unsigned)a.B), dim3(64 * W), lds, p.stream, a);
     }
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 // the re-fit launch of the flagged problems (fit_kernel<..., RESCUE>): up to kFitRescueGrid of them, one workgroup each; entries
@@ -1615,34 +1632,10 @@ template <typename T, class M, int R, int W = 1> int launch_fit_rescue(const Lau
     } else {
         if (p.w || p.t_stride != 0 || !p.rescue) return VP_ERR_UNSUPPORTED;
         FitArgs<T, M> a;
-        if (!bind_model(*p.model, a.mdl)) return VP_ERR_UNSUPPORTED;
-        a.t = (const T *)p.t;
-        a.w = nullptr;
-        a.yw = (const T *)p.yw;
-        a.alpha = (T *)p.alpha_out;
-        a.C_out = (T *)p.C_out;
-        a.cost_out = p.cost_out;
-        a.status = p.status;
-        a.report = p.report;
-        a.m = p.m;
-        a.B = p.B;
-        a.t_stride = 0;
-        a.w_stride = 0;
-        a.eps = (T)p.eps;
-        a.ftol = (T)p.opts->ftol;
-        a.xtol = (T)p.opts->xtol;
-        a.gtol = (T)p.opts->gtol;
-        a.stepbound = (T)p.opts->stepbound;
-        a.patience = p.opts->patience;
-        a.scale_diag = p.opts->scale_diag;
-        a.trace = p.trace;
-        a.trace_rows = p.trace_rows;
-        a.grid_uniform = p.grid_uniform;
-        a.rescue = p.rescue;
-        a.rescue_slot = p.rescue_slot;
+        if (!fill_fit_args(p, a)) return VP_ERR_UNSUPPORTED; // (w null, t_stride 0 by the test above; w_stride is not read without w)
         const size_t lds = fit_lds_bytes<T, M, R, W>(false);
         hipLaunchKernelGGL((fit_kernel<T, M, R, W, false, 0, true>), dim3(kFitRescueGrid), dim3(64 * W), lds, p.stream, a);
-        return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+        return launch_status();
     }
 }
 
@@ -1705,7 +1698,7 @@ template <typename T, class M, int R, int W = 1> int launch_best_fit(const Launc
     a.t_stride = p.t_stride;
     if (a.nprob <= 0) return VP_ERR_OK;
     hipLaunchKernelGGL((best_fit_kernel<T, M, R, W>), dim3((unsigned)a.nprob), dim3(64 * W), 0, p.stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 } // namespace vp

@@ -1080,10 +1080,10 @@ fit2_kernel(const Fit2Args<T, M> args) {
             store_rows<T, R, W>(s_t, MP, lane, true, tmp);
         }
         if (threadIdx.x == 0) {
-            kc->ftol = a.ftol;
-            kc->xtol = a.xtol;
-            kc->gtol = a.gtol;
-            kc->stepbound = a.stepbound;
+            kc->ftol = a.lm.ftol;
+            kc->xtol = a.lm.xtol;
+            kc->gtol = a.lm.gtol;
+            kc->stepbound = a.lm.stepbound;
             kc->alpha = a.alpha;
             kc->rescue = a.rescue;
             kc->rescue_slot = a.rescue_slot;
@@ -1097,8 +1097,8 @@ fit2_kernel(const Fit2Args<T, M> args) {
             kc->queue = args.queue;
             kc->B = a.B;
             kc->trace_rows = a.trace_rows;
-            kc->scale_diag = a.scale_diag;
-            kc->max_fev = a.patience * (Q + 1);
+            kc->scale_diag = a.lm.scale_diag;
+            kc->max_fev = a.lm.patience * (Q + 1);
             kc->m = a.m;
 #ifdef VP_FIT2_CLOCKS
             for (int i = 0; i < 6; ++i) kc->sck[i] = 0;
@@ -1393,31 +1393,8 @@ template <typename T, class M, int R, int W = 1> int launch_fit2(const LaunchPar
             return launch_fit<T, M, R, W>(p);
         Fit2Args<T, M> args;
         FitArgs<T, M> &a = args.f;
-        if (!bind_model(*p.model, a.mdl)) return VP_ERR_UNSUPPORTED;
-        a.t = (const T *)p.t;
-        a.w = nullptr;
-        a.yw = (const T *)p.yw;
-        a.alpha = (T *)p.alpha_out;
-        a.C_out = (T *)p.C_out;
-        a.cost_out = p.cost_out;
-        a.status = p.status;
-        a.report = p.report;
-        a.m = p.m;
-        a.B = p.B;
-        a.t_stride = 0;
-        a.w_stride = 0;
-        a.eps = (T)p.eps;
-        a.ftol = (T)p.opts->ftol;
-        a.xtol = (T)p.opts->xtol;
-        a.gtol = (T)p.opts->gtol;
-        a.stepbound = (T)p.opts->stepbound;
-        a.patience = p.opts->patience;
-        a.scale_diag = p.opts->scale_diag;
-        a.trace = p.trace;
-        a.trace_rows = p.trace_rows;
-        a.grid_uniform = p.grid_uniform;
-        a.rescue = p.rescue;
-        a.rescue_slot = p.rescue_slot;
+        static_assert(M::kStatic, "the slot kernels are built for static models: fill_fit_args reorders no column of theirs");
+        if (!fill_fit_args(p, a)) return VP_ERR_UNSUPPORTED; // (w null, t_stride 0 by the test above; w_stride is not read without w)
         if (a.B <= 0) return VP_ERR_OK;
         // (W == 1 slot kernels of fit_rescue_v models re-fit what they flag themselves: no list, no second launch)
         if (p.rescue_used && !fit2_self_rescue_v<T, M, W>) *p.rescue_used = 1;
@@ -1444,10 +1421,11 @@ template <typename T, class M, int R, int W = 1> int launch_fit2(const LaunchPar
         hipLaunchKernelGGL((fit2_kernel<T, M, R, W, PADM_, GS, NG, WPS>), dim3((unsigned)(blocks * (NG / NGK))),        \
                            dim3(64 * W * NGK), lds_k, p.stream, args);                                                 \
     } while (0)
-        if (p.m == 64 * R * W) {
+        const int padm = padding_variant(p.m, R, W);
+        if (padm == 1) {
             record_fit(p, kFitKernelSlots, 1, false);
             VP_F2(1);
-        } else if (R > 2 && p.m > 64 * (R - 2) * W) {
+        } else if (padm == 2) {
             record_fit(p, kFitKernelSlots, 2, false);
             VP_F2(2);
         } else {
@@ -1455,7 +1433,7 @@ template <typename T, class M, int R, int W = 1> int launch_fit2(const LaunchPar
             VP_F2(0);
         }
 #undef VP_F2
-        return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+        return launch_status();
     }
 }
 

@@ -1128,6 +1128,7 @@ __global__ void __launch_bounds__(64 * VP_FITG2_WAVES, VP_FITG2_WAVES == 8 ? 2 :
 template <class M> int launch_fitg(const LaunchParams &p, double *dbg = nullptr) {
     if (p.S != 1 || !p.queue) return VP_ERR_UNSUPPORTED;
     FitgArgs a;
+    std::memset(&a, 0, sizeof a);
     a.t = (const float *)p.t;
     a.w = (const float *)p.w;
     a.yw = (const float *)p.yw;
@@ -1171,7 +1172,7 @@ template <class M> int launch_fitg(const LaunchParams &p, double *dbg = nullptr)
     else if (uniform) hipLaunchKernelGGL((fitg2_kernel<M, NS, true, true>), grid, block, 0, p.stream, a);
     else if (!weighted) hipLaunchKernelGGL((fitg2_kernel<M, NS, false, false>), grid, block, 0, p.stream, a);
     else hipLaunchKernelGGL((fitg2_kernel<M, NS, false, true>), grid, block, 0, p.stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 } // namespace vp

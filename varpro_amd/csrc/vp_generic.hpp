@@ -1191,14 +1191,7 @@ template <typename T> inline bool fill_args(const LaunchParams &p, GenArgs<T> &a
     a.t_stride = p.t_stride;
     a.w_stride = p.w_stride;
     a.eps = (T)p.eps;
-    if (p.opts) {
-        a.lm.ftol = (T)p.opts->ftol;
-        a.lm.xtol = (T)p.opts->xtol;
-        a.lm.gtol = (T)p.opts->gtol;
-        a.lm.stepbound = (T)p.opts->stepbound;
-        a.lm.patience = p.opts->patience;
-        a.lm.scale_diag = p.opts->scale_diag;
-    }
+    if (p.opts) a.lm = lm_opts_from<T>(*p.opts);
     a.trace = p.trace;
     a.trace_rows = p.trace_rows;
     a.list = p.gen_list;
@@ -1246,7 +1239,7 @@ template <typename T> int launch_evaluate(const LaunchParams &p) {
     const size_t lds = gen_lds_for<T>(a, &gen_evaluate_kernel<T>);
     if (p.S > 1) record_global_stream(p, 1, kGlobalGeneric, 0);
     hipLaunchKernelGGL((gen_evaluate_kernel<T>), dim3((unsigned)p.gen_blocks), dim3(TB), lds, p.stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 template <typename T> int launch_fit(const LaunchParams &p) {
     GenArgs<T> a;
@@ -1256,7 +1249,7 @@ template <typename T> int launch_fit(const LaunchParams &p) {
     const size_t lds = gen_lds_for<T>(a, &gen_fit_kernel<T>);
     record_fit(p, kFitKernelGeneric, -1, p.w != nullptr);
     hipLaunchKernelGGL((gen_fit_kernel<T>), dim3((unsigned)p.gen_blocks), dim3(TB), lds, p.stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 template <typename T> size_t mrhs_lm_state_bytes() { return sizeof(LmAny<T>); }
 template <typename T> int launch_mrhs_fit(const LaunchParams &p) {
@@ -1272,20 +1265,17 @@ template <typename T> int launch_mrhs_fit(const LaunchParams &p) {
     const size_t lds = gen_lds_for<T>(a, &gen_mrhs_fit_kernel<T>);
     record_global_stream(p, 0, kGlobalGeneric, 0);
     hipLaunchKernelGGL((gen_mrhs_fit_kernel<T>), dim3((unsigned)p.gen_blocks), dim3(TB), lds, p.stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 template <typename T> int launch_basis(const LaunchParams &p) {
     GenArgs<T> a;
     if (!fill_args(p, a)) return VP_ERR_UNSUPPORTED;
     a.skip_invariant = (p.basis_flags & VP_BASIS_SKIP_INVARIANT) ? 1 : 0;
-    int ncols = 0;
-    for (int j = 0; j < p.model->n_basis; ++j)
-        if (!(a.skip_invariant && p.model->kind[j] == VP_BASIS_CONST)) ++ncols;
-    a.n_phi_cols = ncols;
+    a.n_phi_cols = phi_column_count(*p.model, a.skip_invariant != 0);
     if (a.B <= 0) return VP_ERR_OK;
     const unsigned grid = (unsigned)(a.B < 4096 ? a.B : 4096);
     hipLaunchKernelGGL((gen_basis_kernel<T>), dim3(grid), dim3(TB), 0, p.stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 template <typename T> int launch_best_fit(const LaunchParams &p) {
     GenArgs<T> a;
@@ -1295,7 +1285,7 @@ template <typename T> int launch_best_fit(const LaunchParams &p) {
     const int64_t nprob = a.B * p.S;
     const unsigned grid = (unsigned)(nprob < 4096 ? nprob : 4096);
     hipLaunchKernelGGL((gen_best_fit_kernel<T>), dim3(grid), dim3(TB), 0, p.stream, a, (int)p.S);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 template <typename T> int launch_stats(const LaunchParams &p) {
@@ -1310,7 +1300,7 @@ template <typename T> int launch_stats(const LaunchParams &p) {
     sa.status_out = p.stats_status;
     if (sa.g.B <= 0) return VP_ERR_OK;
     hipLaunchKernelGGL((gen_stats_kernel<T>), dim3((unsigned)p.gen_blocks), dim3(TB), 0, p.stream, sa);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 } // namespace gen

@@ -512,7 +512,7 @@ template <typename T> int launch_gstats(const GStatsParams &p) {
         if (gx > 0x7fffffff) return VP_ERR_UNSUPPORTED;
         hipLaunchKernelGGL((gstats_blocks_kernel<T>), dim3((unsigned)gx), dim3(TB), 0, p.stream, a);
     }
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 } // namespace gs

@@ -83,12 +83,7 @@ template <typename T> int ext_fit_step_t(const ExtFitParams &p) {
     a.B = p.B;
     a.w_stride = p.w_stride;
     a.eps = (T)p.eps;
-    a.o.ftol = (T)p.opts.ftol;
-    a.o.xtol = (T)p.opts.xtol;
-    a.o.gtol = (T)p.opts.gtol;
-    a.o.stepbound = (T)p.opts.stepbound;
-    a.o.patience = p.opts.patience;
-    a.o.scale_diag = p.opts.scale_diag;
+    a.o = lm_opts_from<T>(p.opts);
     a.init = p.init;
     a.lazy = p.lazy;
     a.vec = host_aligned<T>((int)p.m, {p.phi, p.dphi, p.w, p.yw}) ? 1 : 0;

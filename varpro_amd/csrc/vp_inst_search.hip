@@ -48,7 +48,7 @@ int search_loop_update(const double *cost, const int32_t *status, int64_t k, int
     if (B <= 0) return VP_ERR_OK;
     hipLaunchKernelGGL(search::loop_update_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, cost, status, (int)k, B,
                        best, index);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 } // namespace vp

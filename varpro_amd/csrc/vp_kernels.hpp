@@ -6,7 +6,9 @@
 //                     HBM-roofline fraction BASELINE.json asks for) == src/model/mod.rs:308,359-362
 //   fit_kernel      : device-resident Levenberg-Marquardt over the VarPro functional (vp_fit.hpp)
 #pragma once
+#include <cstring>
 #include <initializer_list>
+#include <type_traits>
 
 #include "vp_core.hpp"
 
@@ -109,6 +111,34 @@ struct LaunchParams {
     int gen_scale_cols;      // generic kernels: power-of-two scaling of huge basis columns (and their derivative columns)
     hipStream_t stream;
 };
+
+// what a launcher returns after its launch
+inline int launch_status() { return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP; }
+
+// the LM options in a kernel's scalar type (the argument records of the fit kernels; lm_after_eval / lm_next_step, vp_lm_core.hpp)
+template <typename T> struct LmOpts {
+    T ftol, xtol, gtol, stepbound;
+    int patience;
+    int scale_diag;
+};
+template <typename T> inline LmOpts<T> lm_opts_from(const vp_lm_opts &o) {
+    LmOpts<T> r;
+    r.ftol = (T)o.ftol;
+    r.xtol = (T)o.xtol;
+    r.gtol = (T)o.gtol;
+    r.stepbound = (T)o.stepbound;
+    r.patience = o.patience;
+    r.scale_diag = o.scale_diag;
+    return r;
+}
+
+// columns per problem of a Phi output: every basis function, or all but the constant ones
+inline int phi_column_count(const vp_model_desc &d, bool skip_invariant) {
+    int ncols = 0;
+    for (int j = 0; j < d.n_basis; ++j)
+        if (!(skip_invariant && d.kind[j] == VP_BASIS_CONST)) ++ncols;
+    return ncols;
+}
 
 // vp_debug_last_fit's record: which fit kernel a launcher issued (include/varpro_hip_debug.h)
 enum { kFitKernelWave = 1, kFitKernelSlots = 2, kFitKernelGram = 3, kFitKernelBlock = 4, kFitKernelGeneric = 5 };
@@ -702,9 +732,11 @@ template <class M> inline bool bind_model(const vp_model_desc &d, M &out) {
     }
 }
 
-template <typename T, class M, int R, int W = 1> int launch_evaluate(const LaunchParams &p) {
-    EvalArgs<T, M> a;
-    if (!bind_model(*p.model, a.mdl)) return VP_ERR_UNSUPPORTED;
+// the evaluation kernels' argument record (resident and blocked family); false: the descriptor does not match M
+template <typename T, class M> inline bool fill_eval_args(const LaunchParams &p, EvalArgs<T, M> &a) {
+    static_assert(std::is_trivially_copyable_v<EvalArgs<T, M>>, "kernel argument records are filled byte-wise");
+    std::memset(&a, 0, sizeof a);
+    if (!bind_model(*p.model, a.mdl)) return false;
     a.t = (const T *)p.t;
     a.w = (const T *)p.w;
     a.yw = (const T *)p.yw;
@@ -721,6 +753,12 @@ template <typename T, class M, int R, int W = 1> int launch_evaluate(const Launc
     a.w_stride = p.w_stride;
     a.eps = (T)p.eps;
     a.grid_uniform = p.grid_uniform;
+    return true;
+}
+
+template <typename T, class M, int R, int W = 1> int launch_evaluate(const LaunchParams &p) {
+    EvalArgs<T, M> a;
+    if (!fill_eval_args(p, a)) return VP_ERR_UNSUPPORTED;
     if (a.nprob <= 0) return VP_ERR_OK;
     dim3 grid((unsigned)a.nprob), block(64 * W);
     // run-time-descriptor models only get the element-wise (any alignment) variants: half the instantiations of a
@@ -732,19 +770,19 @@ template <typename T, class M, int R, int W = 1> int launch_evaluate(const Launc
             if constexpr (eval2_split<T, M, R, W, 2, true, true>()) {
                 if (!p.w && p.m == 64 * R * W) { // a full-length, unweighted problem: the split kernel
                     hipLaunchKernelGGL((evaluate_kernel<T, M, R, W, 2, true, false, true, true>), grid, block, 0, p.stream, a);
-                    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+                    return launch_status();
                 }
             }
             if (p.w) hipLaunchKernelGGL((evaluate_kernel<T, M, R, W, 2, true, true, true>), grid, block, 0, p.stream, a);
             else hipLaunchKernelGGL((evaluate_kernel<T, M, R, W, 2, true, false, true>), grid, block, 0, p.stream, a);
-            return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+            return launch_status();
         }
     }
     if constexpr (eval2_split<T, M, R, W, 1, true, true>()) {
         // set_params (+ residuals) of a full-length, unweighted problem on a uniform grid: phase 1 of the split kernel
         if (mode < 2 && aligned && p.grid_uniform != 0 && !p.w && p.m == 64 * R * W) {
             hipLaunchKernelGGL((evaluate_kernel<T, M, R, W, 1, true, false, true, true>), grid, block, 0, p.stream, a);
-            return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+            return launch_status();
         }
     }
     const int variant = (mode == 0 ? 1 : mode) * 4 + (aligned ? 2 : 0) + (p.w ? 1 : 0);
@@ -759,7 +797,7 @@ template <typename T, class M, int R, int W = 1> int launch_evaluate(const Launc
         VP_EV(2, 0, 0) VP_EV(2, 0, 1) VP_EV(2, 1, 0) VP_EV(2, 1, 1)
     }
 #undef VP_EV
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 template <typename T, class M, int R, int W = 1> int launch_basis(const LaunchParams &p) {
@@ -771,10 +809,7 @@ template <typename T, class M, int R, int W = 1> int launch_basis(const LaunchPa
     a.dPhi_out = (T *)p.dPhi_out;
     a.m = p.m;
     a.skip_invariant = (p.basis_flags & VP_BASIS_SKIP_INVARIANT) ? 1 : 0;
-    int ncols = 0;
-    for (int j = 0; j < p.model->n_basis; ++j)
-        if (!(a.skip_invariant && p.model->kind[j] == VP_BASIS_CONST)) ++ncols;
-    a.n_phi_cols = ncols;
+    a.n_phi_cols = phi_column_count(*p.model, a.skip_invariant != 0);
     a.B = p.B;
     a.t_stride = p.t_stride;
     if (a.B <= 0) return VP_ERR_OK;
@@ -787,13 +822,13 @@ template <typename T, class M, int R, int W = 1> int launch_basis(const LaunchPa
             if (host_aligned<T>(p.m, {p.t, p.Phi_out, p.dPhi_out}) && a.n_phi_cols == NE && M::P == NE &&
                 a.B * NE * bpp < ((int64_t)1 << 31)) {
                 hipLaunchKernelGGL((basis_flat_kernel<M>), dim3((unsigned)(a.B * NE * bpp)), dim3(256), 0, p.stream, a, bpp);
-                return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+                return launch_status();
             }
         }
 #endif
         if (host_aligned<T>(p.m, {p.t, p.Phi_out, p.dPhi_out}) && a.B * bpp < ((int64_t)1 << 31)) {
             hipLaunchKernelGGL((basis_rowpair_kernel<M>), dim3((unsigned)(a.B * bpp)), dim3(256), 0, p.stream, a, bpp);
-            return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+            return launch_status();
         }
     }
 #endif
@@ -802,7 +837,7 @@ template <typename T, class M, int R, int W = 1> int launch_basis(const LaunchPa
     if (host_aligned<T>(p.m, {p.t, p.Phi_out, p.dPhi_out}))
         hipLaunchKernelGGL((basis_kernel<T, M, R, W, true>), grid, block, 0, p.stream, a);
     else hipLaunchKernelGGL((basis_kernel<T, M, R, W, false>), grid, block, 0, p.stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 } // namespace vp

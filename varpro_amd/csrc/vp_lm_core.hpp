@@ -28,11 +28,7 @@ template <typename T, int N, int Q> struct LmVars {
     int accepted; // the latest evaluation became the new best point (outputs of lm_after_eval)
 };
 
-template <typename T> struct LmOpts {
-    T ftol, xtol, gtol, stepbound;
-    int patience;
-    int scale_diag;
-};
+// (the options record LmOpts<T> of both steps: vp_kernels.hpp, next to the launch parameters it is filled from)
 
 template <typename T, int N, int Q> __device__ __forceinline__ void lm_init(LmVars<T, N, Q> &s, const T *alpha0) {
 #pragma unroll

@@ -1406,24 +1406,28 @@ template <typename T, class M, int R> constexpr bool mrhs_one_wave_spills() {
     return (M::N + 1 + M::P) * R * (int)(sizeof(T) / 4) > 400;
 }
 
+// few problems: factorisation and LM step are pure latency -> 4 waves per problem (R / 4 rows per lane, in pairs: R % 8 == 0);
+// ALWAYS four waves where the columns of a problem do not fit the registers of one (the one-wave form of the triple
+// exponential at 32 rows per lane spilled 596 VGPRs)
+template <typename T, class M, int R> constexpr bool mrhs_four_waves(int64_t B) {
+    return R % 8 == 0 && (B <= 1024 || mrhs_one_wave_spills<T, M, R>());
+}
+
 template <typename T, class M, int R> int launch_mrhs_factor(const LaunchParams &p) {
     MrhsFactorArgs<T, M> a;
     if (!fill_factor_args<T, M>(p, a)) return VP_ERR_UNSUPPORTED;
-    // few problems: the factorisation is pure latency -> 4 waves per problem (R/4 rows per lane); ALWAYS four waves where
-    // the columns of a problem do not fit the registers of one (the one-wave form of the triple exponential at 32 rows per
-    // lane spilled 596 VGPRs)
-    if constexpr (R % 8 == 0) { // (R / 4 rows per lane, in pairs)
-        if (a.B <= 1024 || mrhs_one_wave_spills<T, M, R>()) {
+    if constexpr (R % 8 == 0) { // (the four-wave kernel exists for these sets only)
+        if (mrhs_four_waves<T, M, R>(a.B)) {
             record_global_waves(p, kGlobalFactorWaves, 4);
             hipLaunchKernelGGL((mrhs_factor_kernel<T, M, R / 4, 4>), dim3((unsigned)a.B), dim3(256), 0, p.stream, a);
-            return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+            return launch_status();
         }
     }
     if constexpr (!(R % 8 == 0 && mrhs_one_wave_spills<T, M, R>())) {
         record_global_waves(p, kGlobalFactorWaves, 1);
         hipLaunchKernelGGL((mrhs_factor_kernel<T, M, R, 1>), dim3((unsigned)a.B), dim3(64), 0, p.stream, a);
     }
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 template <typename T, class M, int R> int launch_mrhs_stream(const LaunchParams &p) {
@@ -1462,7 +1466,7 @@ template <typename T, class M, int R> int launch_mrhs_stream(const LaunchParams 
                 hipLaunchKernelGGL((mrhs_coop_out_kernel<T, N, P, RWd, NWd, 2, 1>), dim3((unsigned)((int64_t)gxo * p.B)), dim3(64 * NWd), 0, p.stream, a);
             else
                 hipLaunchKernelGGL((mrhs_coop_out_kernel<T, N, P, RWd, NWd, 1, 2>), dim3((unsigned)((int64_t)gxo * p.B)), dim3(64 * NWd), 0, p.stream, a);
-            return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+            return launch_status();
         }
 #endif
         if (p.mrhs_mode == 0 && vec) {
@@ -1476,7 +1480,7 @@ template <typename T, class M, int R> int launch_mrhs_stream(const LaunchParams 
             record_global_stream(p, p.mrhs_mode, kGlobalCoopDma, gx);
             hipLaunchKernelGGL((mrhs_coop_dma_kernel<T, N, P, RWd, NWd, NBd>), dim3((unsigned)((int64_t)gx * p.B)), dim3(64 * NWd), dlds,
                                p.stream, a);
-            return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+            return launch_status();
         }
     }
 #endif
@@ -1496,7 +1500,7 @@ template <typename T, class M, int R> int launch_mrhs_stream(const LaunchParams 
         if (e != hipSuccess) return VP_ERR_HIP;
         hipLaunchKernelGGL((mrhs_stream_kernel<T, N, P, R, 1>), grid, block, lds, p.stream, a);
     }
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 // the LM step + the factorisation of the next trial point (mrhs_step_kernel); p.mrhs_ws = the workspace the LM step reads
@@ -1508,12 +1512,7 @@ template <typename T, class M, int R> int launch_mrhs_lm(const LaunchParams &p) 
     fa.skip_done = 1;
     MrhsLmArgs<T, N, Q, P> a;
     a.ws = *reinterpret_cast<const MrhsWs *>(p.mrhs_ws);
-    a.opts.ftol = (T)p.opts->ftol;
-    a.opts.xtol = (T)p.opts->xtol;
-    a.opts.gtol = (T)p.opts->gtol;
-    a.opts.stepbound = (T)p.opts->stepbound;
-    a.opts.patience = p.opts->patience;
-    a.opts.scale_diag = p.opts->scale_diag;
+    a.opts = lm_opts_from<T>(*p.opts);
     a.alpha0 = (const T *)p.alpha;
     a.io = (const MrhsIo *)p.mrhs_io;
     pair_maps<M>(*p.model, a.pb, a.pp);
@@ -1525,19 +1524,18 @@ template <typename T, class M, int R> int launch_mrhs_lm(const LaunchParams &p) 
     a.gx = p.mrhs_gx > 0 ? p.mrhs_gx : mrhs_gx(p.S, mrhs_gx_cap<T, R>());
     a.trace = p.trace;
     a.trace_rows = p.trace_rows;
-    // few problems: LM step and factorisation are pure latency -> 4 waves per problem (R/4 rows per lane)
-    if constexpr (R % 8 == 0) { // (R / 4 rows per lane, in pairs)
-        if (a.B <= 1024 || mrhs_one_wave_spills<T, M, R>()) {
+    if constexpr (R % 8 == 0) { // (the four-wave kernel exists for these sets only)
+        if (mrhs_four_waves<T, M, R>(a.B)) {
             record_global_waves(p, kGlobalStepWaves, 4);
             hipLaunchKernelGGL((mrhs_step_kernel<T, M, R / 4, 4>), dim3((unsigned)a.B), dim3(256), 0, p.stream, fa, a);
-            return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+            return launch_status();
         }
     }
     if constexpr (!(R % 8 == 0 && mrhs_one_wave_spills<T, M, R>())) {
         record_global_waves(p, kGlobalStepWaves, 1);
         hipLaunchKernelGGL((mrhs_step_kernel<T, M, R, 1>), dim3((unsigned)p.B), dim3(64), 0, p.stream, fa, a);
     }
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 // bytes of one LmVars record (the handle allocates B of them) and final-state extraction
@@ -1605,7 +1603,7 @@ template <typename T, class M, int R> int launch_mrhs_finish(const LaunchParams 
         hipLaunchKernelGGL((mrhs_gather_kernel<T>), dim3((unsigned)((int64_t)gx * p.B)), dim3(256), 0, p.stream, ws, p.B, p.S, (int)M::N,
                            (T *)p.C_out, p.cost_out, p.status, (int)gx, (const MrhsIo *)p.mrhs_io);
     }
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 } // namespace vp

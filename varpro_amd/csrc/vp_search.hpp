@@ -36,6 +36,7 @@
 #include <cstdint>
 
 #include "../../include/varpro_hip.h"
+#include "vp_kernels.hpp" // launch_status()
 
 namespace vp {
 
@@ -398,7 +399,7 @@ template <typename T, int N, bool VEC, bool SCORES> int launch_rank_n(const Rank
     const int64_t blocks = (a.rows + RT * 16 - 1) / (RT * 16);
     if (blocks > 0x7fffffff) return VP_ERR_INVALID;
     hipLaunchKernelGGL((rank_kernel<T, N, RT, VEC, SCORES>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 template <typename T, bool VEC, bool SCORES> int launch_rank_v(const int n, const RankArgs<T> &a, hipStream_t stream) {
     switch (n) {
@@ -433,7 +434,7 @@ template <typename T> int launch_rank(const SearchParams &p) {
         if (rc != VP_ERR_OK) return rc;
         hipLaunchKernelGGL(reduce_scores_kernel<T>, dim3((unsigned)p.B), dim3(256), 0, p.stream, (const T *)p.scores, p.S, p.K,
                            p.Kpad, p.index);
-        return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+        return launch_status();
     }
     return vec ? launch_rank_v<T, true, false>(p.n, a, p.stream) : launch_rank_v<T, false, false>(p.n, a, p.stream);
 }
@@ -442,7 +443,7 @@ template <typename T> int launch_orthonormalize(const SearchParams &p) {
     if (p.K <= 0) return VP_ERR_OK;
     hipLaunchKernelGGL(orthonormalize_kernel<T>, dim3((unsigned)p.K), dim3(256), 0, p.stream, (const T *)p.phi, (const T *)p.w,
                        (T *)p.Q, p.bad, p.n, p.m, p.ldq);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 template <typename T>
@@ -452,7 +453,7 @@ int launch_gather(const void *cand, int64_t K, int q, int per_problem, int64_t k
     if (total <= 0) return VP_ERR_OK;
     hipLaunchKernelGGL(gather_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const T *)cand, K, q,
                        per_problem, k, index, total, (T *)alpha);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 } // namespace search

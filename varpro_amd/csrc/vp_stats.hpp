@@ -151,6 +151,8 @@ __global__ void __launch_bounds__(64 * W) stats_kernel(const StatsArgs<T, M> a) 
 
 template <typename T, class M, int R, int W = 1> int launch_stats(const LaunchParams &p) {
     StatsArgs<T, M> a;
+    static_assert(std::is_trivially_copyable_v<StatsArgs<T, M>>, "kernel argument records are filled byte-wise");
+    std::memset(&a, 0, sizeof a);
     if (!bind_model(*p.model, a.mdl)) return VP_ERR_UNSUPPORTED;
     a.t = (const T *)p.t;
     a.w = (const T *)p.w;
@@ -168,7 +170,7 @@ template <typename T, class M, int R, int W = 1> int launch_stats(const LaunchPa
     a.w_stride = p.w_stride;
     if (a.B <= 0) return VP_ERR_OK;
     hipLaunchKernelGGL((stats_kernel<T, M, R, W>), dim3((unsigned)a.B), dim3(64 * W), 0, p.stream, a);
-    return hipGetLastError() == hipSuccess ? VP_ERR_OK : VP_ERR_HIP;
+    return launch_status();
 }
 
 } // namespace vp
